@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- MSMC-VQ-GAN GAN-phase train step throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line with the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step, ...).  ``--dump-outputs DIR`` also writes what the last timed step returned to its caller
+as ``DIR/<name>.npy``; that step then starts from the seeded initial model (``reset_to_initial_state``), so that every run of
+every build computes it from the same inputs.  ``--full`` adds every other measurement (listed below the contract fields).
 
 N > 1: either launched by ``torch.distributed.run`` (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the
 environment) or directly -- with WORLD_SIZE unset, ``--gpus N`` starts its own N ranks through ``torch.distributed.run`` on
@@ -16,12 +21,13 @@ Workload = BASELINE configs[1]: CSMSC msmc_vq_gan.yaml with 4 heads x 256 codewo
 for the GEMM/conv bodies, fp32 VQ search (indices must be bit-exact).  Weak scaling: per-GPU batch
 fixed.  Rank 0 prints ONE JSON line.
 
-Besides the contract fields the line carries
+With ``--full`` the line also carries
   roofline      the dominant hand-written kernel inside the timed region (HIP events on the launch
                 stream), algorithmic bytes / duration against the gfx950 HBM peak
   vq_microbench the "VQ argmin GB/s" half of the BASELINE metric: msmc_vq_search at N=2^20 frames
   cpu_baseline  the oracle (oracle/step.py, plain PyTorch fp32) timed on this box's host cores on a
                 bounded sample of the same workload (rank 0, N=1 only)
+and the warm-up phase, the fp32 eager step, the per-kernel table and, at N > 1, the secondary gradient-exchange modes.
 """
 import argparse
 import json
@@ -339,6 +345,58 @@ def describe_call(args, kw):
     parts += ['%s=%s' % (k, one(v)) for k, v in kw.items() if k in ('x', 'w', 'g', 'wb', 'geom', 'n_slices') or
               isinstance(v, (int, float))]
     return ' '.join(parts)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, log):
+    """``--dump-outputs``: what the last timed ``train_step`` returned to its caller, one ``<name>.npy`` per tensor or number
+    (nested keys joined with '.'), float64 for 64-bit values and float32 otherwise.  Should they exceed DUMP_LIMIT_BYTES in
+    all, every array larger than its equal share is cut to a fixed (seeded) sample of its flattened elements."""
+    import numpy as np
+    arrays = {}
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                walk('%s.%s' % (prefix, k) if prefix else str(k), v[k])
+        elif torch.is_tensor(v):
+            wide = v.dtype in (torch.float64, torch.int64)
+            arrays[prefix] = v.detach().to('cpu', torch.float64 if wide else torch.float32).numpy()
+        elif isinstance(v, (bool, int, float)):
+            arrays[prefix] = np.asarray(v, dtype=np.float64)
+    walk('', log)
+    if not arrays:
+        raise SystemExit('bench.py: --dump-outputs: the timed step returned no arrays')
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays)
+        for name, a in arrays.items():
+            if a.nbytes > share:
+                keep = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+                arrays[name] = a.reshape(-1)[np.sort(keep)]
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+    say('wrote %d arrays to %s' % (len(arrays), directory))
+
+
+def reset_to_initial_state(model, optimizer, initial):
+    """``--dump-outputs``: put the model back to its seeded initial parameters and buffers and zero the optimizer state, between
+    the timed steps (not timed itself).  The weight gradients accumulate with atomics in an order that varies from run to
+    run, and W + K optimizer steps amplify those last-bit differences; from this state the last timed step computes the same
+    arrays in every run and every build (the forward pass is bit-reproducible), so dumps can be compared output for output."""
+    from msmctts_amd.hip import convnet
+    with torch.no_grad():
+        live = model.state_dict()
+        torch._foreach_copy_([live[k] for k in initial], list(initial.values()))
+        for opt in optimizer.optimizers.values():
+            for st in opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+    convnet.refresh_stale_banks()                # (the weight images follow the parameters now, not inside the timed step)
+    torch.cuda.synchronize()
 
 
 def build(args, device, rank, world):
@@ -677,22 +735,33 @@ def bench_predictor(args, device, wd):
         if not tr.use_graphs:
             task.zero_grad()
         return tr.train_step(batch, i)
+    initial = {k: v.detach().clone() for k, v in task.state_dict().items()} if args.dump_outputs else None
     say('built predictor + frozen autoencoder; starting warm-up')
     for i in range(args.warmup):
         step(i)
         torch.cuda.synchronize()
         wd.beat('predictor warm-up %d' % i)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    marks[0].record()
-    for i in range(args.steps):
-        log = step(args.warmup + i)
-        marks[i + 1].record()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed, per_step = 0.0, []
+    head = args.steps - 1 if args.dump_outputs else args.steps      # (the last step of a dump starts from the initial state)
+    for lo, hi in ((0, head), (head, args.steps)):
+        if lo == hi:
+            continue
+        if lo:
+            reset_to_initial_state(task, tr.optimizer, initial)
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(hi - lo + 1)]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        marks[0].record()
+        for i in range(lo, hi):
+            log = step(args.warmup + i)
+            marks[i - lo + 1].record()
+        torch.cuda.synchronize()
+        elapsed += time.perf_counter() - t0
+        per_step += [marks[i].elapsed_time(marks[i + 1]) for i in range(hi - lo)]
+    per_step.sort()
     wd.beat('predictor timed steps')
-    per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, log)
     ms_per_step = elapsed / args.steps * 1e3
     ms_instr = None
     graphs_were = tr.use_graphs
@@ -768,7 +837,7 @@ def bench_predictor(args, device, wd):
                                           % (nsample, sample_frames, args.cpu_steps, args.cpu_warmup, threads, cores, cpu_model(), torch.__version__),
                                    s_per_step=sec, cpu_model=cpu_model())
         out['speedup_vs_cpu'] = out['value'] / out['cpu_baseline']['value']
-    print(emit_line(out, args.kernels_out))
+    print(emit_line(out, args.kernels_out if args.full else None))      # (no per-kernel table without --full: no side file)
 
 
 def self_spawn(argv, n, job_timeout, capture=False):
@@ -933,6 +1002,15 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them returned (the losses of the step) as DIR/<name>.npy '
+                         '(rank 0); the batch and the window positions are seeded and, outside the clock, the model is put back to its seeded '
+                         'initial state before that step, so the same arguments give the same inputs and the same arrays')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also run the other measurements: per-kernel table and rooflines (--kernel-timing-steps), '
+                         'warm-up phase (--warmup-phase-steps), fp32 eager steps (--fp32-steps), VQ micro-benchmarks (--no-microbench), '
+                         'the CPU oracle (--cpu-steps) and, at N > 1, the secondary gradient-exchange modes (--exchange).  Without '
+                         '--full none of them runs, whatever their own options say')
     ap.add_argument('--config', type=int, default=2, choices=[1, 2, 3, 4, 5],
                     help='BASELINE.json configuration (msmctts_amd/configs.py BASELINE_CONFIGS): 2 = the headline (CSMSC, 2 stages, '
                          '4 heads x 256, B=16, one GPU); 1 = 1 stage, 1 head x 64, B=4; 3 = the LJSpeech-named copy of #2 meant for '
@@ -992,6 +1070,11 @@ def main():
     ap.add_argument('--fp32-steps', type=int, default=3,
                     help='eager fp32 steps (the parity configuration) timed after the headline, 0 = skip')
     args = ap.parse_args()
+    if not args.full:
+        args.kernel_timing_steps = args.warmup_phase_steps = args.fp32_steps = args.cpu_steps = 0
+        args.no_microbench = True
+        if args.exchange in ('auto', 'both', 'all'):      # (the headline's exchange; the other modes are secondary)
+            args.exchange = 'serial'
     from msmctts_amd.configs import BASELINE_CONFIGS
     preset = BASELINE_CONFIGS[args.config]
     args.model_kw = dict(preset['model'])
@@ -1068,7 +1151,9 @@ def main():
                                             vq_microbench(device, 4, 64, iters=5), vq_microbench(device, 8, 512, iters=5)]}))
         return
     cfg, trainer = build(args, device, rank, world)
-    state0 = {k: v.detach().clone() for k, v in trainer.model.state_dict().items()} if rank == 0 and world == 1 else None
+    state0 = ({k: v.detach().clone() for k, v in trainer.model.state_dict().items()}
+              if rank == 0 and world == 1 and args.cpu_steps > 0 else None)      # (the weights the CPU oracle starts from)
+    initial = {k: v.detach().clone() for k, v in trainer.model.state_dict().items()} if args.dump_outputs else None
     batch = make_batch(args.batch, args.frames, args.in_dim, 300, seed=1234, rank=rank, device='cpu')
     lengths_host = batch['mel_length'].tolist()
     batch = {k: v.to(device) for k, v in batch.items()}
@@ -1109,27 +1194,35 @@ def main():
                        'gradient_exchange': None if world == 1 else (args.exchange if args.graph else 'bucketed from hooks')},
         }
 
-    def timed_steps(first):
+    def timed_steps(first, reset_last=False):
         '''exactly K steps between barrier + synchronize on both sides; per-step durations from events recorded on the step's
         stream between the steps (no host synchronisation inside the timed region: the headline stays the wall clock over all
-        K steps; the events give the median SURVEY 8d asks for)'''
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-        t0 = time.perf_counter()
-        marks[0].record()
-        for i in range(args.steps):
-            log_ = step(first + i)
-            marks[i + 1].record()
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
+        K steps; the events give the median SURVEY 8d asks for).  ``reset_last`` (--dump-outputs): the clock stops before the
+        last step, the model returns to its initial state (reset_to_initial_state), and the last step is timed on its own'''
+        def fence():
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            torch.cuda.synchronize()
+        dt, per, log_ = 0.0, [], None
+        head = args.steps - 1 if reset_last else args.steps
+        for lo, hi in ((0, head), (head, args.steps)):
+            if lo == hi:
+                continue
+            if lo:
+                reset_to_initial_state(trainer.model, trainer.optimizer, initial)
+            fence()
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(hi - lo + 1)]
+            t0 = time.perf_counter()
+            marks[0].record()
+            for i in range(lo, hi):
+                log_ = step(first + i)
+                marks[i - lo + 1].record()
+            fence()
+            dt += time.perf_counter() - t0
+            per += [marks[i].elapsed_time(marks[i + 1]) for i in range(hi - lo)]
         wd.beat('timed steps')
-        return dt, sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)), log_
+        return dt, sorted(per), log_
 
     def over_ranks(dt):
         '''(max over ranks, per-rank ms/step)'''
@@ -1140,7 +1233,9 @@ def main():
         dist.all_gather(every, tt)
         return max(float(t) for t in every), [float(t) / args.steps * 1e3 for t in every]
 
-    elapsed, per_step, log = timed_steps(args.warmup)
+    elapsed, per_step, log = timed_steps(args.warmup, reset_last=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, log)     # (before the --full measurements run further steps)
     exchange_modes = None
     core = {}
     if (secondary or child_overlap) and world > 1 and args.graph:
@@ -1350,7 +1445,7 @@ def main():
                                    s_per_step=sec, cpu_model=cpu_model(),
                                    warmup_phase=dict(value=sample_frames / wsec, unit='mel-frames/s', s_per_step=wsec))
         out['speedup_vs_cpu'] = value / out['cpu_baseline']['value']
-    print(emit_line(out, args.kernels_out))
+    print(emit_line(out, args.kernels_out if args.full else None))      # (no per-kernel table without --full: no side file)
     sys.stdout.flush()
     if world > 1:
         if core:

@@ -484,7 +484,7 @@ def test_bench_two_ranks_sharing_the_gpu_run_the_whole_data_parallel_path():
 
 
 def test_bench_two_ranks_time_the_secondary_exchange_modes_under_the_guard():
-    """``--exchange all`` (what ``auto`` resolves to at N > 1 over RCCL) on the shared GPU over gloo: the headline's reductions
+    """``--full --exchange all`` (what ``auto`` resolves to at N > 1 over RCCL under ``--full``) on the shared GPU over gloo: the headline's reductions
     over ranks happen BEFORE the secondary modes, the bf16-wire mode is timed after it under ``Watchdog.guard``, the third mode
     as a child job of rank 0, all three reported in ``exchange_modes``; one line, exit code 0."""
     import json, subprocess, sys, os
@@ -494,7 +494,7 @@ def test_bench_two_ranks_time_the_secondary_exchange_modes_under_the_guard():
     # GPU, the test hook makes the child a gloo / serial job -- what is checked is the orchestration and the merged line)
     env['MSMC_BENCH_CHILD_ARGS'] = '--share-gpu --backend gloo --exchange serial'
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--share-gpu', '--backend', 'gloo', '--batch', '4',
-                          '--steps', '3', '--warmup', '2', '--no-microbench', '--cpu-steps', '0', '--fp32-steps', '0', '--exchange', 'all',
+                          '--steps', '3', '--warmup', '2', '--full', '--no-microbench', '--cpu-steps', '0', '--fp32-steps', '0', '--exchange', 'all',
                           '--kernel-timing-steps', '0', '--warmup-phase-steps', '0', '--stall-timeout', '240', '--job-timeout', '500'],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

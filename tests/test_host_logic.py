@@ -193,6 +193,28 @@ def test_bench_line_is_one_short_parseable_json_line(tmp_path):
     assert slim['cpu_baseline']['value'] == full['cpu_baseline']['value']
 
 
+def test_bench_dump_outputs_writes_what_the_step_returned(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs DIR``: every tensor / number of the structure ``train_step`` returned becomes
+    ``DIR/<dotted name>.npy`` with its values, float32 (float64 for 64-bit values); above the size limit each array larger
+    than its share is cut to the same seeded sample on every call, so two builds can be compared file by file."""
+    import numpy as np
+    import bench
+    log = {'loss': {'mel': torch.tensor(1.25, dtype=torch.bfloat16), 'vq': torch.arange(6, dtype=torch.float64).reshape(2, 3), 'n': 3},
+           'big': torch.arange(4096, dtype=torch.float32)}
+    bench.dump_outputs(str(tmp_path / 'a'), log)
+    got = {f[:-4]: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    assert set(got) == {'loss.mel', 'loss.vq', 'loss.n', 'big'}
+    assert got['loss.mel'].dtype == np.float32 and got['loss.mel'] == 1.25
+    assert got['loss.vq'].dtype == np.float64 and np.array_equal(got['loss.vq'], np.arange(6.0).reshape(2, 3))
+    assert got['loss.n'] == 3.0 and np.array_equal(got['big'], np.arange(4096, dtype=np.float32))
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4096)
+    bench.dump_outputs(str(tmp_path / 'b'), log)
+    bench.dump_outputs(str(tmp_path / 'c'), log)
+    small = {f[:-4]: np.load(str(tmp_path / 'b' / f)) for f in os.listdir(str(tmp_path / 'b'))}
+    assert sum(a.nbytes for a in small.values()) <= 4096 and small['big'].size == 256 and len(set(small['big'])) == 256
+    assert np.array_equal(small['loss.vq'], got['loss.vq']) and np.array_equal(small['big'], np.load(str(tmp_path / 'c' / 'big.npy')))
+
+
 def _header_struct_fields(name):
     """[(field, kind)] of ``typedef struct <name> {...}`` in include/msmc_hip.h; kind: 'p' pointer, 'i' int, 'f' float,
     'l' long, ('i', n) int array"""

@@ -22,16 +22,18 @@ tune)
   RETUNE=${RETUNE:-gather7} python tools/tune_bench_shapes.py 2>&1 | tail -3
   export MSMC_TUNE_CACHE=$PWD/gpurun_out/tuned_gfx950.json ;;
 bench)
-  python bench.py --kernels-out gpurun_out/${TAG}_bench_kernels.json --calls-out gpurun_out/${TAG}_layer_table.json --cpu-steps 0 --fp32-steps 0 --no-microbench --warmup-phase-steps 0 --steps 30 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.log || tail -20 gpurun_out/${TAG}_bench.log
+  OUT=${OUT:-${TMPDIR:-/tmp}/msmc_bench}; mkdir -p $OUT
+  python bench.py --full --kernels-out $OUT/${TAG}_bench_kernels.json --calls-out $OUT/${TAG}_layer_table.json --cpu-steps 0 --fp32-steps 0 --no-microbench --warmup-phase-steps 0 --steps 30 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.log || tail -20 $OUT/${TAG}_bench.log
   python - <<PY
 import json
-d=json.load(open('gpurun_out/${TAG}_bench.json')); print('ms/step', d['ms_per_step'], 'median', d['ms_per_step_median'], 'roofline_step', d['roofline_step']['frac'])
-k=json.load(open('gpurun_out/${TAG}_bench_kernels.json'))['kernels']
+d=json.load(open('$OUT/${TAG}_bench.json')); print('ms/step', d['ms_per_step'], 'median', d['ms_per_step_median'], 'roofline_step', d['roofline_step']['frac'])
+k=json.load(open('$OUT/${TAG}_bench_kernels.json'))['kernels']
 for n,v in sorted(k.items(), key=lambda kv:-kv[1]['ms_per_step'])[:26]: print('%.3f %5.1f %6.1f %s' % (v['ms_per_step'], v['launches']/3, v['avg_us'], n[:70]))
 PY
   ;;
 bench4)
-  python bench.py --config 4 --kernels-out gpurun_out/${TAG}_bench_config4_kernels.json --steps 10 --warmup 3 --cpu-steps ${CPU_STEPS:-2} --cpu-warmup 1 > gpurun_out/${TAG}_bench_config4.json 2> gpurun_out/${TAG}_bench_config4.log || tail -n 25 gpurun_out/${TAG}_bench_config4.log
-  cut -c1-1500 gpurun_out/${TAG}_bench_config4.json ;;
+  OUT=${OUT:-${TMPDIR:-/tmp}/msmc_bench}; mkdir -p $OUT
+  python bench.py --full --config 4 --kernels-out $OUT/${TAG}_bench_config4_kernels.json --steps 10 --warmup 3 --cpu-steps ${CPU_STEPS:-2} --cpu-warmup 1 > $OUT/${TAG}_bench_config4.json 2> $OUT/${TAG}_bench_config4.log || tail -n 25 $OUT/${TAG}_bench_config4.log
+  cut -c1-1500 $OUT/${TAG}_bench_config4.json ;;
 esac
 done
