@@ -567,6 +567,30 @@ int msmc_tanh_bwd(const void* y, const void* g, void* gx, long n, int dtype, msm
  * hifigan/generator.py:52-54 -- and its backward gx (compute dtype) = g (fp32) * (1 - y^2) */
 int msmc_tanh_f32_fwd(const void* x, float* y, long n, int dtype, msmc_stream stream);
 int msmc_tanh_f32_bwd(const float* y, const float* g, void* gx, long n, int dtype, msmc_stream stream);
+/* BatchNorm over frames: nn.BatchNorm1d(C, eps, momentum, affine=False) of the normalised quantiser (``norm: True``, reference
+ * vqgantts/msmc_vqgan.py:115-123, 177-178) on channels-last rows x [N][C] (``dtype``: 0 fp32, 1 bf16), statistics per channel
+ * over all N rows in fp32.  C % 8 == 0 and C <= 1024, x / y / g / gx / mean / rstd / workspace 16-byte aligned, N < 2^31:
+ * MSMC_E_SHAPE otherwise.  Every sum runs in a fixed order (no atomics): two calls on the same input are bit-identical.
+ * Bytes of scratch the two training passes need for these sizes (0 for a refused shape). */
+size_t msmc_bn_workspace(long N, int C);
+/* Training forward, two launches: per-slab (count, mean, M2) into the workspace (Welford; never E[x^2] - E[x]^2), then Chan's
+ * merge of the slabs and y = (x - mean) * rstd with the biased variance.  y is written in ``out_dtype``: ``dtype`` or 0 (fp32 for
+ * the fp32 VQ search behind it).  mean / rstd [C] fp32 are kept for the backward pass; running_mean / running_var (both or
+ * neither) are blended with ``momentum`` (running_var from the unbiased variance) and num_batches_tracked (int64, may be NULL)
+ * is incremented, all on the device.  N < 2: MSMC_E_SHAPE (one value per channel has no variance). */
+int msmc_bn_fwd(const void* x, void* y, float* mean, float* rstd, float* running_mean, float* running_var,
+                long long* num_batches_tracked, void* workspace, size_t workspace_bytes, long N, int C, float eps, float momentum,
+                int dtype, int out_dtype, msmc_stream stream);
+/* Evaluation forward, one launch: y = (x - running_mean) / sqrt(running_var + eps); rstd [C] (may be NULL) receives
+ * 1 / sqrt(running_var + eps) for the evaluation backward. */
+int msmc_bn_eval_fwd(const void* x, const float* running_mean, const float* running_var, void* y, float* rstd, long N, int C,
+                     float eps, int dtype, int out_dtype, msmc_stream stream);
+/* Training backward, two launches: per-slab sum(g) and sum(g * xhat) into the workspace, then
+ * gx = rstd * (g - sum(g) / N - xhat * sum(g * xhat) / N) in ``dtype``; g in ``g_dtype``: ``dtype`` or 0 (fp32). */
+int msmc_bn_bwd(const void* g, const void* x, const float* mean, const float* rstd, void* gx, void* workspace,
+                size_t workspace_bytes, long N, int C, int g_dtype, int dtype, msmc_stream stream);
+/* Evaluation backward: gx = g * rstd, with the rstd the evaluation forward wrote. */
+int msmc_bn_eval_bwd(const void* g, const float* rstd, void* gx, long N, int C, int g_dtype, int dtype, msmc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * O1  gradient-norm clipping + AdamW for all tensors of one child in three launches (csrc/optim.hip).

@@ -577,6 +577,349 @@ __global__ __launch_bounds__(256) void fft_prologue_kernel(const TI* __restrict_
     if (key_bias && t == T - 1 && lane < Tp - T) key_bias[(size_t)b * Tp + T + lane] = ninf;      // (Tp - T < 32)
 }
 
+// ---- BatchNorm over frames (the normalised quantiser) -----------------------------------------------------------
+// nn.BatchNorm1d(C, eps, momentum, affine=False) behind the two 1x1 convolutions of a stage's pre-processor (reference
+// vqgantts/msmc_vqgan.py:115-123, applied at :177-178), on channels-last rows x [N][C]: statistics per channel over all N rows,
+// padding included.  A row is read as 16-byte vectors (V = 4 fp32 / 8 bf16 channels per lane); a workgroup owns a contiguous slab
+// of rows and its 256 lanes are R = min(256 / (C / V), 32) rows in flight.  Every reduction is two-level in a fixed order (lane r
+// walks its rows / partials in order, the R lanes of a channel are then added in order through LDS), no atomics: two runs are
+// bit-identical.  The variance is never formed as E[x^2] - E[x]^2: lanes keep Welford's (count, mean, M2), and partial results
+// are merged with Chan's formula.
+template <typename T> struct bn_vec { static constexpr int V = 4; };
+template <> struct bn_vec<unsigned short> { static constexpr int V = 8; };
+
+template <int V> MSMC_DEV void bn_ld(const float* p, long i, float (&o)[V]) {
+#pragma unroll
+    for (int h = 0; h < V / 4; ++h) {
+        const f32x4 t = *(const f32x4*)(p + i + 4 * h);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[4 * h + q] = t[q];
+    }
+}
+MSMC_DEV void bn_ld(const unsigned short* p, long i, float (&o)[8]) {
+    const u32x4 t = *(const u32x4*)(p + i);
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        o[2 * h] = __uint_as_float(t[h] << 16);
+        o[2 * h + 1] = __uint_as_float(t[h] & 0xffff0000u);
+    }
+}
+template <int V> MSMC_DEV void bn_st(float* p, long i, const float (&v)[V]) {
+#pragma unroll
+    for (int h = 0; h < V / 4; ++h) {
+        f32x4 t;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t[q] = v[4 * h + q];
+        *(f32x4*)(p + i + 4 * h) = t;
+    }
+}
+MSMC_DEV void bn_st(unsigned short* p, long i, const float (&v)[8]) {
+    u32x4 t;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) t[h] = (unsigned)f32_to_bf16_bits(v[2 * h]) | ((unsigned)f32_to_bf16_bits(v[2 * h + 1]) << 16);
+    *(u32x4*)(p + i) = t;
+}
+// (n, mean, m2) <- (n, mean, m2) merged with (nb, mb, m2b): Chan, Golub & LeVeque
+MSMC_DEV void bn_chan(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
+    if (nb == 0.f) return;
+    const float nt = n + nb, d = mb - mean, f = nb / nt;
+    mean = mean + d * f;
+    m2 = (m2 + m2b) + d * d * (n * f);
+    n = nt;
+}
+// lane geometry of a workgroup: G lanes per row, R rows in flight, this lane = (rr, cg); lanes with rr >= R idle
+struct bn_lanes { int G, R, rr, cg; };
+template <int V> MSMC_DEV bn_lanes bn_geometry(int C) {
+    bn_lanes l;
+    l.G = C / V;
+    l.R = 256 / l.G < 32 ? 256 / l.G : 32;
+    l.rr = (int)threadIdx.x / l.G;
+    l.cg = (int)threadIdx.x - l.rr * l.G;
+    return l;
+}
+
+// launch (a): ws[b][0][c] = mean, ws[b][1][c] = M2 of slab b's rows, counts[b] = its row count (int, behind the nblk x 2 x C floats)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, float* __restrict__ ws, long N, int C, long slab,
+                                                       int nblk) {
+    constexpr int V = bn_vec<T>::V;
+    __shared__ float s_mean[256 * V], s_m2[256 * V];
+    __shared__ float s_n[32];
+    const bn_lanes l = bn_geometry<V>(C);
+    const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
+    float mean[V], m2[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) mean[q] = m2[q] = 0.f;
+    int n = 0;
+    if (l.rr < l.R) {
+        for (long row = r0 + l.rr; row < r1; row += 4L * l.R) {
+            float v[4][V];                              // four rows in flight (addresses past the slab clamped, results unused)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const long r = row + (long)u * l.R;
+                bn_ld(x, (r < r1 ? r : r1 - 1) * C + l.cg * V, v[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (row + (long)u * l.R < r1) {
+                    n = n + 1;
+                    const float inv = 1.f / (float)n;
+#pragma unroll
+                    for (int q = 0; q < V; ++q) {
+                        const float d = v[u][q] - mean[q];
+                        mean[q] = mean[q] + d * inv;
+                        m2[q] = m2[q] + d * (v[u][q] - mean[q]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            s_mean[l.rr * C + l.cg * V + q] = mean[q];
+            s_m2[l.rr * C + l.cg * V + q] = m2[q];
+        }
+        if (l.cg == 0) s_n[l.rr] = (float)n;
+    }
+    __syncthreads();
+    if (l.rr == 0) {
+        float cnt[V];
+#pragma unroll
+        for (int q = 0; q < V; ++q) cnt[q] = (float)n;
+        for (int j = 1; j < l.R; ++j) {
+            const float nb = s_n[j];
+#pragma unroll
+            for (int q = 0; q < V; ++q) bn_chan(cnt[q], mean[q], m2[q], nb, s_mean[j * C + l.cg * V + q], s_m2[j * C + l.cg * V + q]);
+        }
+        bn_st<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.cg * V, mean);
+        bn_st<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.cg * V, m2);
+        if (threadIdx.x == 0) ((int*)(ws + (long)nblk * 2 * C))[blockIdx.x] = (int)(r1 - r0);
+    }
+}
+
+// launch (b) (ws != NULL): every workgroup merges the nblk partials in the same fixed order, then normalises its slab; workgroup
+// 0 also writes mean / rstd for the backward pass and advances the running statistics (unbiased variance) and the step counter.
+// Evaluation (ws == NULL): the running statistics instead; rstd_out, where given, keeps 1 / sqrt(running_var + eps).
+template <typename T, typename TO>
+__global__ __launch_bounds__(256) void bn_norm_kernel(const T* __restrict__ x, const float* __restrict__ ws, int nblk,
+                                                      TO* __restrict__ y, float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                      float* running_mean, float* running_var, long long* num_batches_tracked,
+                                                      long N, int C, long slab, float eps, float momentum) {
+    constexpr int V = bn_vec<T>::V;
+    __shared__ float s_mean[256 * V], s_m2[256 * V];
+    __shared__ float s_n[32];
+    const bn_lanes l = bn_geometry<V>(C);
+    if (l.rr >= l.R && !ws) return;
+    float mean[V], rstd[V];
+    if (ws) {
+        float cnt[V], m2[V];
+#pragma unroll
+        for (int q = 0; q < V; ++q) cnt[q] = mean[q] = m2[q] = 0.f;
+        if (l.rr < l.R) {
+            const int* counts = (const int*)(ws + (long)nblk * 2 * C);
+            for (int j = l.rr; j < nblk; j += l.R) {
+                float mb[V], m2b[V];
+                bn_ld<V>(ws, ((long)j * 2 + 0) * C + l.cg * V, mb);
+                bn_ld<V>(ws, ((long)j * 2 + 1) * C + l.cg * V, m2b);
+                const float nb = (float)counts[j];
+#pragma unroll
+                for (int q = 0; q < V; ++q) bn_chan(cnt[q], mean[q], m2[q], nb, mb[q], m2b[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                s_mean[l.rr * C + l.cg * V + q] = mean[q];
+                s_m2[l.rr * C + l.cg * V + q] = m2[q];
+            }
+            if (l.cg == 0) s_n[l.rr] = cnt[0];
+        }
+        __syncthreads();
+        if (l.rr >= l.R) return;
+        // every lane of a channel group merges the R entries itself, in order: the same (mean, M2) in all of them
+#pragma unroll
+        for (int q = 0; q < V; ++q) cnt[q] = mean[q] = m2[q] = 0.f;
+        for (int j = 0; j < l.R; ++j) {
+            const float nb = s_n[j];
+#pragma unroll
+            for (int q = 0; q < V; ++q) bn_chan(cnt[q], mean[q], m2[q], nb, s_mean[j * C + l.cg * V + q], s_m2[j * C + l.cg * V + q]);
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) rstd[q] = 1.f / sqrtf(m2[q] / (float)N + eps);
+        if (blockIdx.x == 0 && l.rr == 0) {
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                const int c = l.cg * V + q;
+                mean_out[c] = mean[q];
+                rstd_out[c] = rstd[q];
+                if (running_mean) {
+                    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean[q];
+                    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (m2[q] / (float)(N - 1));
+                }
+            }
+            if (threadIdx.x == 0 && num_batches_tracked) num_batches_tracked[0] = num_batches_tracked[0] + 1;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            const int c = l.cg * V + q;
+            mean[q] = running_mean[c];
+            rstd[q] = 1.f / sqrtf(running_var[c] + eps);
+            if (rstd_out && blockIdx.x == 0 && l.rr == 0) rstd_out[c] = rstd[q];
+        }
+    }
+    const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
+#pragma unroll 4
+    for (long row = r0 + l.rr; row < r1; row += l.R) {
+        float v[V];
+        bn_ld(x, row * C + l.cg * V, v);
+#pragma unroll
+        for (int q = 0; q < V; ++q) v[q] = (v[q] - mean[q]) * rstd[q];
+        bn_st(y, row * C + l.cg * V, v);
+    }
+}
+
+// backward, launch one: ws[b][0][c] = sum g, ws[b][1][c] = sum g xhat over slab b (xhat recomputed from x, mean, rstd)
+template <typename T, typename TG>
+__global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const TG* __restrict__ g, const T* __restrict__ x,
+                                                           const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                           float* __restrict__ ws, long N, int C, long slab) {
+    constexpr int V = bn_vec<T>::V;
+    __shared__ float s_1[256 * V], s_2[256 * V];
+    const bn_lanes l = bn_geometry<V>(C);
+    const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
+    float s1[V], s2[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) s1[q] = s2[q] = 0.f;
+    if (l.rr < l.R) {
+        float mean[V], rstd[V];
+        bn_ld<V>(mean_in, l.cg * V, mean);
+        bn_ld<V>(rstd_in, l.cg * V, rstd);
+#pragma unroll 4
+        for (long row = r0 + l.rr; row < r1; row += l.R) {
+            float v[V], gv[V];
+            bn_ld(x, row * C + l.cg * V, v);
+            bn_ld(g, row * C + l.cg * V, gv);
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                s1[q] = s1[q] + gv[q];
+                s2[q] = s2[q] + gv[q] * ((v[q] - mean[q]) * rstd[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            s_1[l.rr * C + l.cg * V + q] = s1[q];
+            s_2[l.rr * C + l.cg * V + q] = s2[q];
+        }
+    }
+    __syncthreads();
+    if (l.rr == 0) {
+        for (int j = 1; j < l.R; ++j)
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                s1[q] = s1[q] + s_1[j * C + l.cg * V + q];
+                s2[q] = s2[q] + s_2[j * C + l.cg * V + q];
+            }
+        bn_st<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.cg * V, s1);
+        bn_st<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.cg * V, s2);
+    }
+}
+
+// backward, launch two: the partials added in a fixed order by every workgroup, then gx = rstd (g - sum g / N - xhat sum(g xhat) / N)
+template <typename T, typename TG>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const TG* __restrict__ g, const T* __restrict__ x,
+                                                           const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
+                                                           const float* __restrict__ ws, int nblk, T* __restrict__ gx, long N, int C,
+                                                           long slab) {
+    constexpr int V = bn_vec<T>::V;
+    __shared__ float s_1[256 * V], s_2[256 * V];
+    const bn_lanes l = bn_geometry<V>(C);
+    float s1[V], s2[V];
+#pragma unroll
+    for (int q = 0; q < V; ++q) s1[q] = s2[q] = 0.f;
+    if (l.rr < l.R) {
+        for (int j = l.rr; j < nblk; j += l.R) {
+            float a[V], b[V];
+            bn_ld<V>(ws, ((long)j * 2 + 0) * C + l.cg * V, a);
+            bn_ld<V>(ws, ((long)j * 2 + 1) * C + l.cg * V, b);
+#pragma unroll
+            for (int q = 0; q < V; ++q) { s1[q] = s1[q] + a[q]; s2[q] = s2[q] + b[q]; }
+        }
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            s_1[l.rr * C + l.cg * V + q] = s1[q];
+            s_2[l.rr * C + l.cg * V + q] = s2[q];
+        }
+    }
+    __syncthreads();
+    if (l.rr >= l.R) return;
+#pragma unroll
+    for (int q = 0; q < V; ++q) s1[q] = s2[q] = 0.f;
+    for (int j = 0; j < l.R; ++j)
+#pragma unroll
+        for (int q = 0; q < V; ++q) {
+            s1[q] = s1[q] + s_1[j * C + l.cg * V + q];
+            s2[q] = s2[q] + s_2[j * C + l.cg * V + q];
+        }
+    float mean[V], rstd[V];
+    bn_ld<V>(mean_in, l.cg * V, mean);
+    bn_ld<V>(rstd_in, l.cg * V, rstd);
+#pragma unroll
+    for (int q = 0; q < V; ++q) { s1[q] = s1[q] / (float)N; s2[q] = s2[q] / (float)N; }
+    const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
+#pragma unroll 4
+    for (long row = r0 + l.rr; row < r1; row += l.R) {
+        float v[V], gv[V];
+        bn_ld(x, row * C + l.cg * V, v);
+        bn_ld(g, row * C + l.cg * V, gv);
+#pragma unroll
+        for (int q = 0; q < V; ++q) v[q] = rstd[q] * ((gv[q] - s1[q]) - ((v[q] - mean[q]) * rstd[q]) * s2[q]);
+        bn_st(gx, row * C + l.cg * V, v);
+    }
+}
+
+// evaluation backward: gx = g * rstd (rstd = 1 / sqrt(running_var + eps), as the evaluation forward left it)
+template <typename T, typename TG>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const TG* __restrict__ g, const float* __restrict__ rstd_in,
+                                                          T* __restrict__ gx, long N, int C, long slab) {
+    constexpr int V = bn_vec<T>::V;
+    const bn_lanes l = bn_geometry<V>(C);
+    if (l.rr >= l.R) return;
+    float rstd[V];
+    bn_ld<V>(rstd_in, l.cg * V, rstd);
+    const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
+#pragma unroll 4
+    for (long row = r0 + l.rr; row < r1; row += l.R) {
+        float gv[V];
+        bn_ld(g, row * C + l.cg * V, gv);
+#pragma unroll
+        for (int q = 0; q < V; ++q) gv[q] = gv[q] * rstd[q];
+        bn_st(gx, row * C + l.cg * V, gv);
+    }
+}
+
+// slabs of a pass over N rows: every workgroup of the second launch re-reads all partials (nblk x 2 x C floats) and its own slab
+// (N / nblk rows of C elements) -- the two are balanced near nblk = sqrt(N / 2); at most one slab per CU
+struct bn_grid { int nblk; long slab; };
+static bn_grid bn_slabs(long N) {
+    const long cap = MSMC_NUM_CU > 0 ? MSMC_NUM_CU : 1;
+    long nb = 1;
+    while (nb < cap && (nb + 1) * (nb + 1) * 2 <= N) ++nb;
+    bn_grid gr;
+    gr.slab = N > 0 ? (N + nb - 1) / nb : 1;
+    gr.nblk = N > 0 ? (int)((N + gr.slab - 1) / gr.slab) : 0;
+    return gr;
+}
+static bool bn_shape_ok(long N, int C) { return N >= 0 && N < (1L << 31) && C > 0 && (C % 8) == 0 && C <= 1024; }
+// streaming passes (evaluation): slabs sized for the whole chip, no partials to re-read
+static bn_grid bn_stream_slabs(long N) {
+    const long cap = 8L * MSMC_NUM_CU;
+    long nb = (N + 31) / 32;
+    if (nb > cap) nb = cap;
+    if (nb < 1) nb = 1;
+    bn_grid gr;
+    gr.slab = (N + nb - 1) / nb;
+    gr.nblk = (int)((N + gr.slab - 1) / gr.slab);
+    return gr;
+}
+
 static int nm_grid(long n) {
     long b = (n + 255) / 256;
     const long cap = 8L * MSMC_NUM_CU;
@@ -807,5 +1150,99 @@ int msmc_tanh_bwd(const void* y, const void* g, void* gx, long n, int dtype, msm
     else return MSMC_E_SHAPE;
     return msmc_check_launch();
 }
+
+// ---- BatchNorm over frames ---------------------------------------------------------------------------------------
+size_t msmc_bn_workspace(long N, int C) {
+    if (!bn_shape_ok(N, C)) return 0;
+    const bn_grid gr = bn_slabs(N);
+    return (size_t)gr.nblk * (2 * (size_t)C * sizeof(float) + sizeof(int));
+}
+
+#define BN_ALIGNED(...) (((__VA_ARGS__) & 15) == 0)
+int msmc_bn_fwd(const void* x, void* y, float* mean, float* rstd, float* running_mean, float* running_var,
+                long long* num_batches_tracked, void* workspace, size_t workspace_bytes, long N, int C, float eps, float momentum,
+                int dtype, int out_dtype, msmc_stream stream) {
+    if (!x || !y || !mean || !rstd || (!running_mean != !running_var) || !bn_shape_ok(N, C) || N < 2) return MSMC_E_SHAPE;
+    if (dtype < 0 || dtype > 1 || (out_dtype != dtype && out_dtype != 0)) return MSMC_E_SHAPE;
+    if (!BN_ALIGNED((size_t)x | (size_t)y | (size_t)workspace)) return MSMC_E_SHAPE;
+    if (!workspace || workspace_bytes < msmc_bn_workspace(N, C)) return MSMC_E_WORKSPACE;
+    const bn_grid gr = bn_slabs(N);
+    const dim3 grid((unsigned)gr.nblk);
+    float* ws = (float*)workspace;
+#define BN_FWD(T_, TO_)                                                                                                    \
+    do {                                                                                                                   \
+        MSMC_LAUNCH((bn_stats_kernel<T_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, ws, N, C, gr.slab, gr.nblk); \
+        int rc = msmc_check_launch();                                                                                      \
+        if (rc) return rc;                                                                                                 \
+        MSMC_LAUNCH((bn_norm_kernel<T_, TO_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const float*)ws, gr.nblk, \
+                    (TO_*)y, mean, rstd, running_mean, running_var, num_batches_tracked, N, C, gr.slab, eps, momentum);     \
+    } while (0)
+    if (dtype == 0) BN_FWD(float, float);
+    else if (out_dtype == 0) BN_FWD(unsigned short, float);
+    else BN_FWD(unsigned short, unsigned short);
+#undef BN_FWD
+    return msmc_check_launch();
+}
+
+int msmc_bn_eval_fwd(const void* x, const float* running_mean, const float* running_var, void* y, float* rstd, long N, int C,
+                     float eps, int dtype, int out_dtype, msmc_stream stream) {
+    if (!x || !y || !running_mean || !running_var || !bn_shape_ok(N, C)) return MSMC_E_SHAPE;
+    if (dtype < 0 || dtype > 1 || (out_dtype != dtype && out_dtype != 0)) return MSMC_E_SHAPE;
+    if (!BN_ALIGNED((size_t)x | (size_t)y)) return MSMC_E_SHAPE;
+    if (N == 0) return 0;
+    const bn_grid gr = bn_stream_slabs(N);
+    const dim3 grid((unsigned)gr.nblk);
+#define BN_EVAL(T_, TO_)                                                                                                   \
+    MSMC_LAUNCH((bn_norm_kernel<T_, TO_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const float*)nullptr, 0, \
+                (TO_*)y, (float*)nullptr, rstd, (float*)running_mean, (float*)running_var, (long long*)nullptr, N, C, gr.slab, \
+                eps, 0.f)
+    if (dtype == 0) BN_EVAL(float, float);
+    else if (out_dtype == 0) BN_EVAL(unsigned short, float);
+    else BN_EVAL(unsigned short, unsigned short);
+#undef BN_EVAL
+    return msmc_check_launch();
+}
+
+int msmc_bn_bwd(const void* g, const void* x, const float* mean, const float* rstd, void* gx, void* workspace,
+                size_t workspace_bytes, long N, int C, int g_dtype, int dtype, msmc_stream stream) {
+    if (!g || !x || !mean || !rstd || !gx || !bn_shape_ok(N, C) || N < 2) return MSMC_E_SHAPE;
+    if (dtype < 0 || dtype > 1 || (g_dtype != dtype && g_dtype != 0)) return MSMC_E_SHAPE;
+    if (!BN_ALIGNED((size_t)g | (size_t)x | (size_t)gx | (size_t)mean | (size_t)rstd | (size_t)workspace)) return MSMC_E_SHAPE;
+    if (!workspace || workspace_bytes < msmc_bn_workspace(N, C)) return MSMC_E_WORKSPACE;
+    const bn_grid gr = bn_slabs(N);
+    const dim3 grid((unsigned)gr.nblk);
+    float* ws = (float*)workspace;
+#define BN_BWD(T_, TG_)                                                                                                    \
+    do {                                                                                                                   \
+        MSMC_LAUNCH((bn_bwd_stats_kernel<T_, TG_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const TG_*)g, (const T_*)x, mean, \
+                    rstd, ws, N, C, gr.slab);                                                                              \
+        int rc = msmc_check_launch();                                                                                      \
+        if (rc) return rc;                                                                                                 \
+        MSMC_LAUNCH((bn_bwd_apply_kernel<T_, TG_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const TG_*)g, (const T_*)x, mean, \
+                    rstd, (const float*)ws, gr.nblk, (T_*)gx, N, C, gr.slab);                                              \
+    } while (0)
+    if (dtype == 0) BN_BWD(float, float);
+    else if (g_dtype == 0) BN_BWD(unsigned short, float);
+    else BN_BWD(unsigned short, unsigned short);
+#undef BN_BWD
+    return msmc_check_launch();
+}
+
+int msmc_bn_eval_bwd(const void* g, const float* rstd, void* gx, long N, int C, int g_dtype, int dtype, msmc_stream stream) {
+    if (!g || !rstd || !gx || !bn_shape_ok(N, C)) return MSMC_E_SHAPE;
+    if (dtype < 0 || dtype > 1 || (g_dtype != dtype && g_dtype != 0)) return MSMC_E_SHAPE;
+    if (!BN_ALIGNED((size_t)g | (size_t)gx | (size_t)rstd)) return MSMC_E_SHAPE;
+    if (N == 0) return 0;
+    const bn_grid gr = bn_stream_slabs(N);
+    const dim3 grid((unsigned)gr.nblk);
+#define BN_EBWD(T_, TG_)                                                                                                   \
+    MSMC_LAUNCH((bn_eval_bwd_kernel<T_, TG_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const TG_*)g, rstd, (T_*)gx, N, C, gr.slab)
+    if (dtype == 0) BN_EBWD(float, float);
+    else if (g_dtype == 0) BN_EBWD(unsigned short, float);
+    else BN_EBWD(unsigned short, unsigned short);
+#undef BN_EBWD
+    return msmc_check_launch();
+}
+#undef BN_ALIGNED
 
 }  // extern "C"

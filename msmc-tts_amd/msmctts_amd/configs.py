@@ -13,7 +13,7 @@ def _fft_block_cfg():
 
 
 def csmsc_config(downsample_scales=(1, 4), n_heads=4, embedding_sizes=64, in_dim=80, batch_size=16,
-                 warmup_steps=50000, sample_lengths=12000):
+                 warmup_steps=50000, sample_lengths=12000, norm=False):
     enc = dict(downsample_scales=list(downsample_scales), **_fft_block_cfg())
     return {
         'id': 'msmc_vqgan',
@@ -23,7 +23,7 @@ def csmsc_config(downsample_scales=(1, 4), n_heads=4, embedding_sizes=64, in_dim
                 '_name': 'MSMCVQGAN', 'in_dim': in_dim, 'n_model_size': 256,
                 'encoder_config': enc,
                 'quantizer_config': dict(embedding_sizes=embedding_sizes, embedding_dims=256, n_heads=n_heads,
-                                         prior_config=dict(kernel_size=5, dilation_rate=1, n_layers=1), norm=False),
+                                         prior_config=dict(kernel_size=5, dilation_rate=1, n_layers=1), norm=norm),
                 'frame_decoder_config': _fft_block_cfg(),
                 'pred_mel': True,
                 'decoder_config': dict(upsample_rates=[6, 5, 5, 2], upsample_kernel_sizes=[12, 11, 11, 4],

@@ -170,6 +170,11 @@ _SIGNATURES.update({
     'msmc_tanh_bwd': (_i, [_vp, _vp, _vp, ctypes.c_long, _i, _vp]),
     'msmc_tanh_f32_fwd': (_i, [_vp, _vp, ctypes.c_long, _i, _vp]),
     'msmc_tanh_f32_bwd': (_i, [_vp, _vp, _vp, ctypes.c_long, _i, _vp]),
+    'msmc_bn_workspace': (_sz, [ctypes.c_long, _i]),
+    'msmc_bn_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_long, _i, _f, _f, _i, _i, _vp]),
+    'msmc_bn_eval_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _f, _i, _i, _vp]),
+    'msmc_bn_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_long, _i, _i, _i, _vp]),
+    'msmc_bn_eval_bwd': (_i, [_vp, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp]),
     'msmc_opt_chunk': (_i, []),
     'msmc_opt_clip_adamw': (_i, [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp]),
     'msmc_lrelu_bwd': (_i, [_vp, _vp, _vp, ctypes.c_long, _f, _i, _vp]),

@@ -378,3 +378,85 @@ class _TanhF32(torch.autograd.Function):
 def tanh_f32(x):
     """tanh(x) in fp32 for x in the compute dtype (the cast rides in the kernel, the gradient comes back in x's dtype)"""
     return _TanhF32.apply(x)
+
+
+# ---- BatchNorm over frames: the normalised quantiser (``norm: True``) ---------------------------------------------------
+# nn.BatchNorm1d(C, affine=False) behind a stage's pre-processor (reference vqgantts/msmc_vqgan.py:115-123, 177-178), on the
+# channels-last frames the 1x1 stacks produce -- no transposes.  The module stays the holder of running_mean / running_var /
+# num_batches_tracked (checkpoint keys); the kernels update them on the device, so a captured step replays them.
+def _bn_workspace(bn, N, C, device):
+    """scratch of the two-launch passes, kept on the module: both passes consume it before they return"""
+    nbytes = int(lib.get().msmc_bn_workspace(N, C))
+    ws = getattr(bn, '_hip_ws', None)
+    if ws is None or ws.device != device or ws.numel() * 4 < nbytes:
+        ws = bn._hip_ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
+    return ws
+
+
+class _BatchNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bn, out_fp32):
+        assert x.dtype in _DT and x.is_contiguous()
+        N, C = _rows(x)
+        L = lib.get()
+        y = torch.empty(x.shape, dtype=torch.float32 if out_fp32 else x.dtype, device=x.device)
+        rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+        ctx.training, ctx.bn, ctx.in_dtype = bn.training, bn, x.dtype
+        if bn.training:
+            if N < 2:
+                raise ValueError('Expected more than 1 value per channel when training, got input size %s' % (tuple(x.shape),))
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            ws = _bn_workspace(bn, N, C, x.device)
+            lib.check(L.msmc_bn_fwd(lib.ptr(x), lib.ptr(y), lib.ptr(mean), lib.ptr(rstd), lib.ptr(bn.running_mean, torch.float32),
+                                    lib.ptr(bn.running_var, torch.float32), lib.ptr(bn.num_batches_tracked, torch.int64),
+                                    lib.ptr(ws), ws.numel() * 4, N, C, float(bn.eps), float(bn.momentum), _DT[x.dtype],
+                                    _DT[y.dtype], lib.stream(x)), 'msmc_bn_fwd')
+            ctx.save_for_backward(x, mean, rstd)
+        else:
+            lib.check(L.msmc_bn_eval_fwd(lib.ptr(x), lib.ptr(bn.running_mean, torch.float32), lib.ptr(bn.running_var, torch.float32),
+                                         lib.ptr(y), lib.ptr(rstd), N, C, float(bn.eps), _DT[x.dtype], _DT[y.dtype],
+                                         lib.stream(x)), 'msmc_bn_eval_fwd')
+            ctx.save_for_backward(rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        if g.dtype != torch.float32 and g.dtype != ctx.in_dtype:
+            g = g.to(ctx.in_dtype)
+        L = lib.get()
+        gx = torch.empty(g.shape, dtype=ctx.in_dtype, device=g.device)
+        N, C = _rows(g)
+        if ctx.training:
+            x, mean, rstd = ctx.saved_tensors
+            ws = _bn_workspace(ctx.bn, N, C, g.device)
+            lib.check(L.msmc_bn_bwd(lib.ptr(g), lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(gx), lib.ptr(ws), ws.numel() * 4,
+                                    N, C, _DT[g.dtype], _DT[ctx.in_dtype], lib.stream(g)), 'msmc_bn_bwd')
+        else:
+            rstd, = ctx.saved_tensors
+            lib.check(L.msmc_bn_eval_bwd(lib.ptr(g), lib.ptr(rstd), lib.ptr(gx), N, C, _DT[g.dtype], _DT[ctx.in_dtype],
+                                         lib.stream(g)), 'msmc_bn_eval_bwd')
+        return gx, None, None
+
+
+def batch_norm_usable(x, bn):
+    """can ``batch_norm`` run this module on x [..., C]?  fp32 / bf16 frames, C % 8 == 0 and <= 1024, and the module the reference
+    builds: affine=False, a float momentum (None is torch's cumulative average), running statistics kept in fp32 on x's device"""
+    C = x.shape[-1]
+    if not (x.dtype in _DT and (x.is_cuda or lib._host_pointers_ok) and C % 8 == 0 and 0 < C <= 1024 and C == bn.num_features):
+        return False
+    if bn.affine or not bn.track_running_stats or not isinstance(bn.momentum, float):
+        return False
+    if x.is_contiguous() and x.data_ptr() % 16:             # (rows are read as 16-byte vectors)
+        return False
+    return all(t is not None and t.dtype == dt and t.device == x.device and t.is_contiguous()
+               for t, dt in ((bn.running_mean, torch.float32), (bn.running_var, torch.float32),
+                             (bn.num_batches_tracked, torch.int64)))
+
+
+def batch_norm(x, bn_module, out_fp32=False):
+    """``bn_module`` (nn.BatchNorm1d, affine=False) applied to channels-last x [B, T, C] -- what the reference computes through
+    ``.transpose(1, 2)``: batch statistics over all B T frames and the module's buffers updated in training, the running statistics
+    in evaluation.  ``out_fp32``: the result in fp32 whatever x's dtype (the VQ search reads fp32 frames); the gradient returns in
+    x's dtype.  Two launches per training pass, one per evaluation pass."""
+    return _BatchNorm.apply(x.contiguous(), bn_module, bool(out_fp32))

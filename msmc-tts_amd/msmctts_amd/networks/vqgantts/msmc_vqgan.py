@@ -148,7 +148,7 @@ class MultiStageQuantizer(nn.Module):
                 k = u * 2 if u % 2 == 0 else u * 2 + 1
                 self.transposed_conv.append(nn.ConvTranspose1d(n_model_size, n_model_size, k, u, padding=(k - u) // 2))
         self.hip_dtype = torch.float32        # compute dtype of the HIP GEMMs (trainer: bfloat16 in bf16 runs)
-        self.use_hip = not norm            # (the normalised variant -- no shipped configuration uses it -- keeps stock operators)
+        self.use_hip = True                # (False, set by hand: every layer of the quantiser on stock operators)
         self._bank = None
 
     # -- the 1x1 channel GEMMs, the prior predictor's WaveNet stack and their Tanh / gate on the gfx950 kernels ---------
@@ -182,6 +182,17 @@ class MultiStageQuantizer(nn.Module):
         h = hipnorm.tanh(hip_conv(bank, pair[0], x.unsqueeze(1)))
         return hip_conv(bank, pair[1], h).squeeze(1)
 
+    def _norm_hip(self, stage, x):
+        """the BatchNorm1d behind a stage's pre-processor (``norm=True``, reference msmc_vqgan.py:115-123) on channels-last
+        frames: two launches of hip/norm.py, fp32 out for the search; a module the kernels do not cover runs as the reference
+        runs it, on the transposed view"""
+        pre = self.preprocessor[stage]
+        if len(pre) < 4:
+            return x
+        if hipnorm.batch_norm_usable(x, pre[3]):
+            return hipnorm.batch_norm(x, pre[3], out_fp32=True)
+        return pre[3](x.transpose(1, 2)).transpose(1, 2)
+
     def forward(self, encoder_states, from_encoder=True):
         states = list(encoder_states)
         if from_encoder:
@@ -209,7 +220,7 @@ class MultiStageQuantizer(nn.Module):
             elif from_encoder:
                 pre_in = emb if residual is None else torch.cat((emb, residual), dim=-1)
                 q_in = (_pointwise_stack(self.preprocessor[i], pre_in) if hip is None else
-                        self._stack_hip(bank, stages[i][0], pre_in.to(dt).contiguous()))
+                        self._norm_hip(i, self._stack_hip(bank, stages[i][0], pre_in.to(dt).contiguous())))
             else:
                 q_in = emb
             quant, dff, ind = self.quantizer[i](q_in, length, update=self.update_codebook)
