@@ -57,6 +57,11 @@ static const char* msmc_kname(const char* base, const char* elt, int a, int b) {
 }
 #define MSMC_GROUP_LIMIT 16         // members one grouped call may carry (split into launches of <= MSMC_GROUP_MAX)
 extern "C" int msmc_conv_gather(const msmc_conv_desc* d, msmc_stream stream);
+// a descriptor any entry point accepts
+static bool cv_desc_ok(const msmc_conv_desc* d) { return d->B > 0 && d->Cin > 0 && d->Cout > 0 && d->QH > 0 && d->QW > 0; }
+// result of a one-descriptor family launcher from the status of its launch: 1 = launched, < 0 error (0, does not apply, is
+// the launcher's own answer)
+static int cv_launched(int rc) { return rc ? (rc < 0 ? rc : -rc) : 1; }
 static int msmc_gather_generation = 2;          // 1 = first-generation forward / data-gradient kernels (A/B tests)
 extern "C" void msmc_conv_set_gather_generation(int n) { msmc_gather_generation = n; }
 static int msmc_wgrad_generation = 2;           // 1 = first-generation bf16 weight-gradient kernel (A/B tests)
@@ -818,6 +823,74 @@ static int cv_geometry(const msmc_conv_desc* d, CvGeom* G, int elt_bytes, int XS
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Grouped launch of ONE kernel family (the members of msmc_conv_gather_group it owns).  A family is a traits struct F next
+// to its kernel:
+//   F::Plan, F::Args        plan of one member (fields applies, lds) / argument block of the family's group kernel
+//   F::min_members          members a call must hold before the family groups (fewer: left to the paths after it)
+//   F::lone_single          a member left alone in its bucket runs the single kernel here (false: left to the paths after it)
+//   F::mine(d)              the member is the family's
+//   F::plan(d, pl, share)   plan of one member; share = the family's members in the call, at most MSMC_GROUP_MAX
+//   F::same(p, q)           the two plans run one kernel instantiation, so they may share a grid
+//   F::blocks(p)            workgroups the member contributes
+//   F::head(a, m)           stores the member count, returns first[]
+//   F::fill(a, k, d, p)     slot k of the argument block (all of it but first[k])
+//   F::dispatch(p, blocks, lds, stream, d, group)      the single kernel on d (group == NULL) or the group kernel; sets
+//                           msmc_conv_last
+// ------------------------------------------------------------------------------------------------
+// fill-and-dispatch step: members[0..m) (plans pl[members[k]], one kernel instantiation) as one launch
+template <class F>
+static int cv_family_dispatch(const msmc_conv_desc* descs, const typename F::Plan* pl, const int* members, int m,
+                              msmc_stream stream) {
+    typename F::Args a;
+    int* first = F::head(a, m);
+    int blocks = 0;
+    size_t lds = 0;
+    for (int k = 0; k < m; ++k) {
+        const int j = members[k];
+        first[k] = blocks;
+        F::fill(a, k, descs[j], pl[j]);
+        blocks += F::blocks(pl[j]);
+        if (pl[j].lds > lds) lds = pl[j].lds;
+    }
+    first[m] = blocks;
+    ++msmc_conv_launches;
+    return F::dispatch(pl[members[0]], blocks, lds, stream, m == 1 ? &descs[members[0]] : nullptr, m == 1 ? nullptr : &a);
+}
+// plan every member of the family, bucket the plans that may share a grid (MSMC_GROUP_MAX per launch), launch the buckets in
+// member order.  done[i]: launched (here or by a family before this one); a member whose plan does not apply is MSMC_E_SHAPE.
+template <class F>
+static int cv_family_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stream, bool* done) {
+    typename F::Plan pl[MSMC_GROUP_LIMIT];
+    bool todo[MSMC_GROUP_LIMIT];
+    int count = 0;
+    for (int i = 0; i < n; ++i) {
+        todo[i] = !done[i] && F::mine(&descs[i]);
+        count += todo[i];
+    }
+    if (count < F::min_members) return 0;
+    for (int i = 0; i < n; ++i) {
+        if (!todo[i]) continue;
+        int rc = F::plan(&descs[i], &pl[i], count < MSMC_GROUP_MAX ? count : MSMC_GROUP_MAX);
+        if (rc) return rc;
+        if (!pl[i].applies) return MSMC_E_SHAPE;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!todo[i]) continue;
+        int members[MSMC_GROUP_MAX], m = 0;
+        for (int j = i; j < n && m < MSMC_GROUP_MAX; ++j) {
+            if (!todo[j] || !F::same(pl[i], pl[j])) continue;
+            members[m++] = j;
+            todo[j] = false;
+        }
+        if (m == 1 && !F::lone_single) continue;
+        for (int k = 0; k < m; ++k) done[members[k]] = true;
+        int rc = cv_family_dispatch<F>(descs, pl, members, m, stream);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 #include "gather3.inc"
 #include "gather4.inc"
 #include "gemm1.inc"
@@ -977,6 +1050,24 @@ static int cv2_dispatch(int nt, int ckm, int sb, dim3 grid, size_t lds, msmc_str
     msmc_conv_last = msmc_prof_name(msmc_kname2(grp ? "conv_gather2_group_kernel" : "conv_gather2_kernel", EltName<T>::v, nt, ckm, sb));
     return msmc_check_launch();
 }
+// fill-and-dispatch of second-generation members that share a grid (cv_family_dispatch); which members do is decided by
+// cv_group_launch: they adopt the plan of the member with the largest grid
+template <typename T>
+struct Cv2Family {
+    typedef Cv2Plan Plan;
+    typedef CvGroupArgs Args;
+    static bool same(const Plan& p, const Plan& q) { return p.nt == q.nt && p.ckm == q.ckm && p.sb == q.sb; }
+    static int blocks(const Plan& p) { return (int)(p.gx * p.gy); }
+    static int* head(Args& a, int m) { a.n = m; return a.first; }
+    static void fill(Args& a, int k, const msmc_conv_desc& d, const Plan& p) {
+        a.nx[k] = (int)p.gx;
+        a.d[k] = d;
+        a.G[k] = p.G;
+    }
+    static int dispatch(const Plan& p, int blocks, size_t lds, msmc_stream stream, const msmc_conv_desc* d, const Args* group) {
+        return cv2_dispatch<T>(p.nt, p.ckm, p.sb, group ? dim3((unsigned)blocks) : dim3(p.gx, p.gy), lds, stream, d, &p.G, group);
+    }
+};
 
 template <typename T>
 static int cv_launch(const msmc_conv_desc* d, msmc_stream stream) {
@@ -1388,7 +1479,7 @@ template <typename T>
 static int cv_ks_launch(const msmc_conv_desc* d, msmc_stream stream);
 
 extern "C" int msmc_conv_gather(const msmc_conv_desc* d, msmc_stream stream) {
-    if (!d || d->B <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->QH <= 0 || d->QW <= 0) return MSMC_E_SHAPE;
+    if (!d || !cv_desc_ok(d)) return MSMC_E_SHAPE;
     ++msmc_conv_launches;
     // variant 8 = direct kernels (E_SHAPE when none applies); without a tuned variant they are the default for the
     // layers they cover (generation 1 keeps the MFMA kernels everywhere: A/B tests)
@@ -1398,28 +1489,17 @@ extern "C" int msmc_conv_gather(const msmc_conv_desc* d, msmc_stream stream) {
         if (rc != 0) return rc < 0 ? rc : 0;
         if (d->variant == 8) return MSMC_E_SHAPE;
     }
-    if (cv3_is_variant(d->variant)) {           // third generation (bf16): E_SHAPE when the configuration does not apply
-        const int rc = cv3_launch(d, stream);
-        return rc < 0 ? rc : rc == 1 ? 0 : MSMC_E_SHAPE;
-    }
-    if (cv4_is_variant(d->variant)) {           // persistent thin-layer kernel (bf16): E_SHAPE outside its scope
-        const int rc = cv4_launch(d, stream);
-        return rc < 0 ? rc : rc == 1 ? 0 : MSMC_E_SHAPE;
-    }
-    if (g1_is_variant(d->variant)) {            // 1-tap layers as a plain channel GEMM (bf16): E_SHAPE outside its scope
-        const int rc = g1_launch(d, stream);
-        return rc < 0 ? rc : rc == 1 ? 0 : MSMC_E_SHAPE;
-    }
-    if (cv5_is_variant(d->variant)) {           // fifth generation (bf16, sixteen waves, staged taps): E_SHAPE outside its scope
-        const int rc = cv5_launch(d, stream);
-        return rc < 0 ? rc : rc == 1 ? 0 : MSMC_E_SHAPE;
-    }
-    if (cv7_is_variant(d->variant)) {           // seventh generation (bf16, eight waves of 64 x 64, two workgroups per CU): E_SHAPE outside its scope
-        const int rc = cv7_launch(d, stream);
-        return rc < 0 ? rc : rc == 1 ? 0 : MSMC_E_SHAPE;
-    }
-    if (cv6_is_variant(d->variant)) {           // thin-channel kernel (bf16, Cin 8 / 16 / 32, fragments straight from global memory)
-        const int rc = cv6_launch(d, stream);
+    // bf16 kernel families chosen by variant, in this order: third generation, persistent thin-layer kernel, 1-tap layers as
+    // a plain channel GEMM, fifth generation (sixteen waves, staged taps), seventh generation (eight waves of 64 x 64, two
+    // workgroups per CU), thin-channel kernel (fragments straight from global memory).  E_SHAPE outside a family's scope.
+    static const struct {
+        bool (*is_variant)(int);
+        int (*launch)(const msmc_conv_desc*, msmc_stream);
+    } families[] = {{cv3_is_variant, cv3_launch}, {cv4_is_variant, cv4_launch}, {g1_is_variant, g1_launch},
+                    {cv5_is_variant, cv5_launch}, {cv7_is_variant, cv7_launch}, {cv6_is_variant, cv6_launch}};
+    for (const auto& f : families) {
+        if (!f.is_variant(d->variant)) continue;
+        const int rc = f.launch(d, stream);
         return rc < 0 ? rc : rc == 1 ? 0 : MSMC_E_SHAPE;
     }
     if (d->variant == 9) {                      // wave-split deep reduction (E_SHAPE when it does not apply)
@@ -1689,49 +1769,29 @@ static int cv_ks_launch(const msmc_conv_desc* d, msmc_stream stream) {
     rc = cv_ks_dispatch<T>(pl, dim3(pl.gx, pl.gy), pl.lds, stream, d, nullptr);
     return rc ? rc : 1;
 }
-// variant-9 members of a grouped call: one grid per (column tiles, chunk width) configuration.  done[i] = launched here.
+// variant-9 members of a grouped call (cv_family_group_launch): one grid per (column tiles, chunk width) configuration; a
+// lone member of the call keeps the single launch of the per-member path
 template <typename T>
-static int cv_ks_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stream, bool* done) {
-    CvKsPlan pk[MSMC_GROUP_LIMIT];
-    bool todo[MSMC_GROUP_LIMIT];
-    int count = 0;
-    for (int i = 0; i < n; ++i) {
-        done[i] = todo[i] = false;
-        if (descs[i].variant != 9) continue;
-        int rc = cv_ks_plan<T>(&descs[i], &pk[i]);
-        if (rc) return rc;
-        if (!pk[i].applies) return MSMC_E_SHAPE;
-        todo[i] = true;
-        ++count;
+struct CvKsFamily {
+    typedef CvKsPlan Plan;
+    typedef CvKsGroupArgs Args;
+    static constexpr int min_members = 2;
+    static constexpr bool lone_single = true;
+    static bool mine(const msmc_conv_desc* d) { return d->variant == 9; }
+    static int plan(const msmc_conv_desc* d, Plan* pl, int) { return cv_ks_plan<T>(d, pl); }
+    static bool same(const Plan& p, const Plan& q) { return p.nt == q.nt && p.ckm == q.ckm; }
+    static int blocks(const Plan& p) { return (int)(p.gx * p.gy); }
+    static int* head(Args& ga, int m) { ga.a.n = m; return ga.a.first; }
+    static void fill(Args& ga, int k, const msmc_conv_desc& d, const Plan& p) {
+        ga.a.nx[k] = (int)p.gx;
+        ga.a.d[k] = d;
+        ga.a.G[k] = p.G;
+        ga.reg[k] = (int)p.reg;
     }
-    if (count < 2) return 0;                                    // (a lone member: the single launch below)
-    for (int i = 0; i < n; ++i) {
-        if (!todo[i]) continue;
-        CvKsGroupArgs ga;
-        ga.a.n = 0;
-        int blocks = 0;
-        size_t lds = 0;
-        for (int j = i; j < n && ga.a.n < MSMC_GROUP_MAX; ++j) {
-            if (!todo[j] || pk[j].nt != pk[i].nt || pk[j].ckm != pk[i].ckm) continue;
-            ga.a.first[ga.a.n] = blocks;
-            ga.a.nx[ga.a.n] = (int)pk[j].gx;
-            ga.a.d[ga.a.n] = descs[j];
-            ga.a.G[ga.a.n] = pk[j].G;
-            ga.reg[ga.a.n] = (int)pk[j].reg;
-            blocks += (int)(pk[j].gx * pk[j].gy);
-            if (pk[j].lds > lds) lds = pk[j].lds;
-            todo[j] = false;
-            done[j] = true;
-            ++ga.a.n;
-        }
-        ga.a.first[ga.a.n] = blocks;
-        ++msmc_conv_launches;
-        int rc = ga.a.n == 1 ? cv_ks_dispatch<T>(pk[i], dim3(pk[i].gx, pk[i].gy), pk[i].lds, stream, &ga.a.d[0], nullptr)
-                             : cv_ks_dispatch<T>(pk[i], dim3((unsigned)blocks), lds, stream, nullptr, &ga);
-        if (rc) return rc;
+    static int dispatch(const Plan& p, int blocks, size_t lds, msmc_stream stream, const msmc_conv_desc* d, const Args* group) {
+        return cv_ks_dispatch<T>(p, group ? dim3((unsigned)blocks) : dim3(p.gx, p.gy), lds, stream, d, group);
     }
-    return 0;
-}
+};
 
 // which direct kernel would take this descriptor: 0 none, 1 small, 2 dot, 3 outer (mirrors cv_direct_launch)
 static int cv_direct_kind(const msmc_conv_desc* d) {
@@ -1837,84 +1897,24 @@ template <typename T>
 static int cv_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stream) {
     Cv2Plan plans[MSMC_GROUP_LIMIT];
     bool pending[MSMC_GROUP_LIMIT], direct[MSMC_GROUP_LIMIT];
-    // third-generation members: one grid per configuration (tile shape, chunk, halo registers)
-    Cv3Plan p3[MSMC_GROUP_LIMIT];
-    bool gen3[MSMC_GROUP_LIMIT];
-    for (int i = 0; i < n; ++i) {
-        gen3[i] = false;
-        if (!cv3_is_variant(descs[i].variant)) continue;
-        int rc = cv3_plan(&descs[i], descs[i].variant, &p3[i]);
-        if (rc) return rc;
-        if (!p3[i].applies) return MSMC_E_SHAPE;
-        gen3[i] = true;
-    }
-    for (int i = 0; i < n; ++i) {
-        if (!gen3[i]) continue;
-        CvGroupArgs a;
-        a.n = 0;
-        int blocks = 0;
-        size_t lds = 0;
-        for (int j = i; j < n && a.n < MSMC_GROUP_MAX; ++j) {
-            if (!gen3[j] || p3[j].wm != p3[i].wm || p3[j].ntw != p3[i].ntw || p3[j].ckm != p3[i].ckm || p3[j].xv != p3[i].xv ||
-                p3[j].xdma != p3[i].xdma)
-                continue;
-            a.first[a.n] = blocks;
-            a.nx[a.n] = (int)p3[j].gx;
-            a.d[a.n] = descs[j];
-            a.G[a.n] = p3[j].G;
-            blocks += (int)(p3[j].gx * p3[j].gy);
-            if (p3[j].lds > lds) lds = p3[j].lds;
-            gen3[j] = false;
-            ++a.n;
-        }
-        a.first[a.n] = blocks;
-        ++msmc_conv_launches;
-        int rc = a.n == 1 ? cv3_dispatch(p3[i], dim3(p3[i].gx, p3[i].gy), p3[i].lds, stream, &a.d[0], &a.G[0], nullptr)
-                          : cv3_dispatch(p3[i], dim3((unsigned)blocks), lds, stream, nullptr, nullptr, &a);
-        if (rc) return rc;
-    }
-    bool done4[MSMC_GROUP_LIMIT];                               // persistent thin-layer members on one grid (off by default)
-    {
-        const int rc = cv4_group_launch(descs, n, stream, done4);
-        if (rc) return rc;
-    }
-    {
-        bool done5[MSMC_GROUP_LIMIT];                           // fifth-generation members: one grid per configuration
-        const int rc = cv5_group_launch(descs, n, stream, done5);
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) done4[i] = done4[i] || done5[i];
-    }
-    {
-        bool done7[MSMC_GROUP_LIMIT];                           // seventh-generation members: one grid per configuration
-        const int rc = cv7_group_launch(descs, n, stream, done7);
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) done4[i] = done4[i] || done7[i];
-    }
-    {
-        bool done6[MSMC_GROUP_LIMIT];                           // thin-channel members (variant 50): one grid per channel count
-        const int rc = cv6_group_launch(descs, n, stream, done6);
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) done4[i] = done4[i] || done6[i];
-    }
-    {
-        bool dones[MSMC_GROUP_LIMIT];                           // split-bf16 constant-matrix GEMMs (variants 36 / 37): one grid per tile width
-        const int rc = g1s_group_launch(descs, n, stream, dones);
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) done4[i] = done4[i] || dones[i];
-    }
-    {
-        bool doneks[MSMC_GROUP_LIMIT];                          // wave-split members (variant 9): one grid per configuration
-        const int rc = cv_ks_group_launch<T>(descs, n, stream, doneks);
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) done4[i] = done4[i] || doneks[i];
-    }
+    bool done[MSMC_GROUP_LIMIT] = {};                           // members a family below has launched
+    // third generation, persistent thin-layer members on one grid (off by default), fifth and seventh generation, thin-channel
+    // members (variant 50), split-bf16 constant-matrix GEMMs (variants 36 / 37), wave-split members (variant 9)
+    int rc = cv_family_group_launch<Cv3Family>(descs, n, stream, done);
+    if (!rc) rc = cv4_group_launch(descs, n, stream, done);
+    if (!rc) rc = cv_family_group_launch<Cv5Family>(descs, n, stream, done);
+    if (!rc) rc = cv_family_group_launch<Cv7Family>(descs, n, stream, done);
+    if (!rc) rc = cv_family_group_launch<Cv6Family>(descs, n, stream, done);
+    if (!rc) rc = cv_family_group_launch<G1sFamily>(descs, n, stream, done);
+    if (!rc) rc = cv_family_group_launch<CvKsFamily<T>>(descs, n, stream, done);
+    if (rc) return rc;
     for (int i = 0; i < n; ++i) {
         pending[i] = direct[i] = false;
         const msmc_conv_desc* d = &descs[i];
-        if (cv3_is_variant(d->variant) || done4[i]) continue;
+        if (done[i]) continue;
         int nt_unused;
         const bool own_grid = d->variant == 9 || cv4_is_variant(d->variant) || g1_is_variant(d->variant);
-        int rc = (cv_takes_direct(d) || own_grid) ? 0 : cv2_plan<T>(d, &plans[i], &nt_unused);
+        rc = (cv_takes_direct(d) || own_grid) ? 0 : cv2_plan<T>(d, &plans[i], &nt_unused);
         if (rc) return rc;
         if (own_grid) {                                         // (one launch each: they fill the chip on their own)
             rc = msmc_conv_gather(d, stream);
@@ -1940,7 +1940,6 @@ static int cv_group_launch(const msmc_conv_desc* descs, int n, msmc_stream strea
             members[m++] = &descs[j];
             direct[j] = false;
         }
-        int rc;
         if (m == 1) {
             rc = msmc_conv_gather(members[0], stream);
         } else {
@@ -1955,38 +1954,21 @@ static int cv_group_launch(const msmc_conv_desc* descs, int n, msmc_stream strea
         for (int j = 0; j < n; ++j)
             if (pending[j] && (i < 0 || plans[j].gx * plans[j].gy > plans[i].gx * plans[i].gy)) i = j;
         if (i < 0) break;
-        CvGroupArgs a;
-        a.n = 0;
-        int blocks = 0;
-        size_t lds = 0;
-        for (int jj = 0; jj < n && a.n < MSMC_GROUP_MAX; ++jj) {
+        int members[MSMC_GROUP_MAX], m = 0;
+        for (int jj = 0; jj < n && m < MSMC_GROUP_MAX; ++jj) {
             const int j = jj == 0 ? i : (jj <= i ? jj - 1 : jj);          // leader first, then the rest in order
             if (!pending[j]) continue;
-            if (plans[j].nt != plans[i].nt || plans[j].ckm != plans[i].ckm || plans[j].sb != plans[i].sb) {
+            if (!Cv2Family<T>::same(plans[j], plans[i])) {
                 Cv2Plan alt;
-                int rc = cv2_plan_forced<T>(&descs[j], &alt, plans[i].nt, plans[i].ckm, plans[i].sb);
+                rc = cv2_plan_forced<T>(&descs[j], &alt, plans[i].nt, plans[i].ckm, plans[i].sb);
                 if (rc) return rc;
                 if (!alt.applies) continue;
                 plans[j] = alt;
             }
-            a.first[a.n] = blocks;
-            a.nx[a.n] = (int)plans[j].gx;
-            a.d[a.n] = descs[j];
-            a.G[a.n] = plans[j].G;
-            blocks += (int)(plans[j].gx * plans[j].gy);
-            if (plans[j].lds > lds) lds = plans[j].lds;
+            members[m++] = j;
             pending[j] = false;
-            ++a.n;
         }
-        a.first[a.n] = blocks;
-        ++msmc_conv_launches;
-        int rc;
-        if (a.n == 1)
-            rc = cv2_dispatch<T>(plans[i].nt, plans[i].ckm, plans[i].sb, dim3(plans[i].gx, plans[i].gy), plans[i].lds, stream,
-                                 &a.d[0], &a.G[0], nullptr);
-        else
-            rc = cv2_dispatch<T>(plans[i].nt, plans[i].ckm, plans[i].sb, dim3((unsigned)blocks), lds, stream, nullptr, nullptr,
-                                 &a);
+        rc = cv_family_dispatch<Cv2Family<T>>(descs, plans, members, m, stream);
         if (rc) return rc;
     }
     return 0;
@@ -1997,9 +1979,8 @@ extern "C" int msmc_conv_gather_group(const msmc_conv_desc* descs, int n, msmc_s
     if (!descs || n <= 0 || n > MSMC_GROUP_LIMIT) return MSMC_E_SHAPE;
     bool same = true;
     for (int i = 0; i < n; ++i) {
-        const msmc_conv_desc* d = &descs[i];
-        if (d->B <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->QH <= 0 || d->QW <= 0) return MSMC_E_SHAPE;
-        same = same && d->dtype == descs[0].dtype;
+        if (!cv_desc_ok(&descs[i])) return MSMC_E_SHAPE;
+        same = same && descs[i].dtype == descs[0].dtype;
     }
     if (!msmc_conv_grouping || !same || n == 1) {
         for (int i = 0; i < n; ++i) {
@@ -3127,7 +3108,7 @@ static int wg5_launch(const msmc_conv_desc* d, const void* g, float* dw, float* 
 
 extern "C" int msmc_conv_wgrad_ws(const msmc_conv_desc* d, const void* g, float* dw, float* db, void* workspace,
                                   size_t workspace_bytes, msmc_stream stream) {
-    if (!d || !g || !dw || d->B <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->QH <= 0 || d->QW <= 0) return MSMC_E_SHAPE;
+    if (!d || !g || !dw || !cv_desc_ok(d)) return MSMC_E_SHAPE;
     if (d->ntaps <= 0 || d->ntaps > MSMC_CONV_MAX_TAPS) return MSMC_E_SHAPE;
     ++msmc_conv_launches;
     if (d->dtype == 0) return d->variant == 3 ? MSMC_E_SHAPE : wg_launch<float>(d, g, dw, db, stream);
@@ -3176,236 +3157,176 @@ extern "C" size_t msmc_conv_wgrad_workspace(const msmc_conv_desc* d, const void*
     return need3 > need4 ? need3 : need4;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Grouped weight gradients of ONE kernel family.  A family is a traits struct F:
+//   F::Plan, F::Args        plan of one member (P, lds, tpw, gx, gy, gz, ws_floats) / argument block of the group kernel
+//   F::kernel<TPW>          the group kernel for TPW accumulators per wave; F::name, F::name_arg: its symbol as msmc_kname prints it
+//   F::geom(a, k, p)        stores the member's lattice geometry where the argument block carries one
+// and, for the families that select their own members (wg_family_group_launch):
+//   F::owns(gen)            generations the family takes
+//   F::plan(d, g, pl, gen, share)
+// ------------------------------------------------------------------------------------------------
+// the members todo[] (planned, workspace assigned) as launches of at most MSMC_GROUP_MAX members in member order: fill the
+// argument block, launch the kernel of the widest member, then the two-level second stage of the members that split
+template <class F>
+static int wg_group_run(const msmc_conv_desc* descs, const void* const* g, float* const* dw, float* const* db, int n,
+                        const typename F::Plan* pl, bool* todo, msmc_stream stream) {
+    for (int i = 0; i < n; ++i) {
+        if (!todo[i]) continue;
+        typename F::Args a;
+        a.n = 0;
+        int members[MSMC_GROUP_MAX], nmembers = 0;            // members of this launch with a second stage
+        int blocks = 0, tpw = 1;
+        size_t lds = 0;
+        for (int j = i; j < n && a.n < MSMC_GROUP_MAX; ++j) {
+            if (!todo[j]) continue;
+            const int k = a.n++;
+            a.first[k] = blocks;
+            a.nx[k] = (int)pl[j].gx;
+            a.ny[k] = (int)pl[j].gy;
+            a.g[k] = (const unsigned short*)g[j];
+            a.dw[k] = dw[j];
+            a.db[k] = db ? db[j] : nullptr;
+            a.d[k] = descs[j];
+            F::geom(a, k, pl[j]);
+            a.P[k] = pl[j].P;
+            blocks += (int)(pl[j].gx * pl[j].gy * pl[j].gz);
+            if (pl[j].lds > lds) lds = pl[j].lds;
+            if (pl[j].tpw > tpw) tpw = pl[j].tpw;              // the widest member sets the accumulator budget
+            if (pl[j].P.ws) members[nmembers++] = j;
+            todo[j] = false;
+        }
+        a.first[a.n] = blocks;
+        ++msmc_conv_launches;
+        int rc;
+        const dim3 grid((unsigned)blocks);
+#define WGG_GO(TP)                                                                                           \
+    do {                                                                                                     \
+        rc = msmc_allow_lds((const void*)F::template kernel<TP>, (int)lds);                                  \
+        if (rc) return rc;                                                                                   \
+        MSMC_LAUNCH((F::template kernel<TP>), grid, dim3(256), lds, (msmc_stream_t)stream, a);               \
+    } while (0)
+        if (tpw == 1) WGG_GO(1);
+        else if (tpw == 2) WGG_GO(2);
+        else if (tpw == 3) WGG_GO(3);
+        else if (tpw == 4) WGG_GO(4);
+        else WGG_GO(5);
+#undef WGG_GO
+        msmc_conv_last = msmc_prof_name(msmc_kname(F::name, nullptr, tpw, F::name_arg));
+        rc = msmc_check_launch();
+        if (rc) return rc;
+        for (int level = 0; level < 2 && nmembers; ++level) {
+            WgReduceArgs r;
+            r.n = 0;
+            int rblocks = 0;
+            for (int q = 0; q < nmembers; ++q) {
+                const int j = members[q];
+                const msmc_conv_desc& dj = descs[j];
+                float* wsj = pl[j].P.ws;
+                wg3_reduce_add(r, &rblocks, wsj, pl[j].P.ws_stride, (long)dj.ntaps * dj.Cout * dj.Cin,
+                               (db && db[j]) ? dj.Cout : 0, (int)pl[j].gx, wsj + (size_t)pl[j].gx * pl[j].P.ws_stride, dw[j],
+                               db ? db[j] : nullptr, level);
+            }
+            if (!r.n) continue;
+            r.first[r.n] = rblocks;
+            rc = wg3_reduce_launch(r, rblocks, stream);
+            if (rc) return rc;
+        }
+    }
+    return 0;
+}
+// the family's members among those no family has taken yet: when there are several, each is planned for its share of the
+// chip, takes the next region of the workspace and joins the family's grids.  A member whose plan fails stays with the
+// paths after this one.
+template <class F>
+static int wg_family_group_launch(const msmc_conv_desc* descs, const void* const* g, float* const* dw, float* const* db, int n,
+                                  bool* took, float** wsp, size_t* ws_left, msmc_stream stream) {
+    typename F::Plan pl[MSMC_GROUP_LIMIT];
+    bool mine[MSMC_GROUP_LIMIT];
+    int left = 0, count = 0;
+    for (int i = 0; i < n; ++i) {
+        const msmc_conv_desc* d = &descs[i];
+        const int gen = d->variant > 0 ? d->variant : msmc_wgrad_generation;
+        mine[i] = !took[i] && d->dtype == 1 && F::owns(gen) && g[i] && dw[i] && d->B > 0 && d->ntaps > 0 &&
+                  d->ntaps <= MSMC_CONV_MAX_TAPS;
+        left += !took[i];
+        count += mine[i];
+    }
+    if (left <= 1 || count <= 1) return 0;
+    const int share = count < MSMC_GROUP_MAX ? count : MSMC_GROUP_MAX;
+    for (int i = 0; i < n; ++i) {
+        if (!mine[i]) continue;
+        const msmc_conv_desc* d = &descs[i];
+        if (F::plan(d, g[i], &pl[i], d->variant > 0 ? d->variant : msmc_wgrad_generation, share)) { mine[i] = false; continue; }
+        if (pl[i].ws_floats) {
+            if (pl[i].ws_floats > *ws_left) return MSMC_E_WORKSPACE;
+            pl[i].P.ws = *wsp;
+            *wsp += pl[i].ws_floats;
+            *ws_left -= pl[i].ws_floats;
+        }
+        took[i] = true;
+    }
+    return wg_group_run<F>(descs, g, dw, db, n, pl, mine, stream);
+}
+struct Wg5Group {                   // general-lattice LDS-DMA members (variant 7)
+    typedef Wg5Plan Plan;
+    typedef Wg5GroupArgs Args;
+    template <int TPW> static constexpr auto kernel = conv_wgrad5_group_kernel<TPW>;
+    static constexpr const char* name = "conv_wgrad5_group_kernel";
+    static constexpr int name_arg = -1;
+    static void geom(Args& a, int k, const Plan& p) { a.G[k] = p.G; }
+    static bool owns(int gen) { return gen == 7; }
+    static int plan(const msmc_conv_desc* d, const void* g, Plan* pl, int, int share) { return wg5_plan(d, g, pl, share); }
+};
+struct Wg4Group {                   // fourth generation (variants 4 / 5 / 6 inside wgrad4.inc's scope)
+    typedef Wg4Plan Plan;
+    typedef Wg4GroupArgs Args;
+    template <int TPW> static constexpr auto kernel = conv_wgrad4_group_kernel<TPW, 1>;
+    static constexpr const char* name = "conv_wgrad4_group_kernel";
+    static constexpr int name_arg = 1;
+    static void geom(Args&, int, const Plan&) {}
+    static bool owns(int gen) { return gen >= 4 && gen <= 6; }
+    static int plan(const msmc_conv_desc* d, const void* g, Plan* pl, int gen, int share) { return wg4_plan(d, g, pl, gen - 4, share); }
+};
+struct Wg2Group {                   // second / third generation: msmc_conv_wgrad_group_ws4 selects and plans the members
+    typedef Wg2Plan Plan;
+    typedef Wg2GroupArgs Args;
+    template <int TPW> static constexpr auto kernel = conv_wgrad2_group_kernel<TPW>;
+    static constexpr const char* name = "conv_wgrad2_group_kernel";
+    static constexpr int name_arg = -1;
+    static void geom(Args& a, int k, const Plan& p) { a.G[k] = p.G; }
+};
+
 // n independent weight gradients (msmc_conv_wgrad semantics each): bf16 second- / third-generation members share grids.
 // Third-generation members (variant 3) take consecutive regions of the workspace; one grouped second-stage launch
 // folds the partial results of all of them.
-// group4 != 0: fourth-generation members (variants 4 / 5 / 6 inside wgrad4.inc's scope) share grids of their own kernel
-// (conv_wgrad4_group_kernel, every member planned for its share of the chip); 0: they join the shared grid of the
-// second / third generation as third-generation members.  The host layer times both against one launch per member.
+// group4 != 0: variant-7 members, then fourth-generation members (variants 4 / 5 / 6 inside wgrad4.inc's scope) share grids of
+// their own kernels (every member planned for its share of the chip); what they leave goes on as a call of its own would
+// (one member left: a single launch).  0: fourth-generation members join the shared grid of the second / third generation
+// as third-generation members.  The host layer times both against one launch per member.
 extern "C" int msmc_conv_wgrad_group_ws4(const msmc_conv_desc* descs, const void* const* g, float* const* dw,
                                          float* const* db, int n, void* workspace, size_t workspace_bytes,
                                          msmc_stream stream, int group4) {
     if (!descs || !g || !dw || n <= 0 || n > MSMC_GROUP_LIMIT) return MSMC_E_SHAPE;
     Wg2Plan plans[MSMC_GROUP_LIMIT];
-    bool pending[MSMC_GROUP_LIMIT];
+    bool pending[MSMC_GROUP_LIMIT], took[MSMC_GROUP_LIMIT] = {};
     float* wsp = (float*)workspace;
     size_t ws_left = workspace_bytes / sizeof(float);
-    if (group4 && msmc_conv_grouping && n > 1) {                // general-lattice LDS-DMA members (variant 7) first
-        Wg5Plan p5[MSMC_GROUP_LIMIT];
-        bool mine5[MSMC_GROUP_LIMIT], took5[MSMC_GROUP_LIMIT];
-        int count5 = 0;
-        for (int i = 0; i < n; ++i) {
-            const msmc_conv_desc* d = &descs[i];
-            const int gen = d->variant > 0 ? d->variant : msmc_wgrad_generation;
-            took5[i] = false;
-            mine5[i] = d->dtype == 1 && gen == 7 && g[i] && dw[i] && d->B > 0 && d->ntaps > 0 && d->ntaps <= MSMC_CONV_MAX_TAPS;
-            if (mine5[i]) ++count5;
-        }
-        if (count5 > 1) {
-            const int share = count5 < MSMC_GROUP_MAX ? count5 : MSMC_GROUP_MAX;
-            for (int i = 0; i < n; ++i) {
-                if (!mine5[i]) continue;
-                if (wg5_plan(&descs[i], g[i], &p5[i], share)) { mine5[i] = false; continue; }
-                if (p5[i].ws_floats) {
-                    if (p5[i].ws_floats > ws_left) return MSMC_E_WORKSPACE;
-                    p5[i].P.ws = wsp;
-                    wsp += p5[i].ws_floats;
-                    ws_left -= p5[i].ws_floats;
-                }
-            }
-            for (int i = 0; i < n; ++i) {
-                if (!mine5[i]) continue;
-                Wg5GroupArgs a;
-                a.n = 0;
-                int members[MSMC_GROUP_MAX], nmembers = 0;
-                int blocks = 0, tpw = 1;
-                size_t lds = 0;
-                for (int j = i; j < n && a.n < MSMC_GROUP_MAX; ++j) {
-                    if (!mine5[j]) continue;
-                    const int k = a.n++;
-                    a.first[k] = blocks;
-                    a.nx[k] = (int)p5[j].gx;
-                    a.ny[k] = (int)p5[j].gy;
-                    a.g[k] = (const unsigned short*)g[j];
-                    a.dw[k] = dw[j];
-                    a.db[k] = db ? db[j] : nullptr;
-                    a.d[k] = descs[j];
-                    a.G[k] = p5[j].G;
-                    a.P[k] = p5[j].P;
-                    blocks += (int)(p5[j].gx * p5[j].gy * p5[j].gz);
-                    if (p5[j].lds > lds) lds = p5[j].lds;
-                    if (p5[j].tpw > tpw) tpw = p5[j].tpw;
-                    if (p5[j].P.ws) members[nmembers++] = j;
-                    mine5[j] = false;
-                    took5[j] = true;
-                }
-                a.first[a.n] = blocks;
-                ++msmc_conv_launches;
-                int rc;
-                const dim3 grid((unsigned)blocks);
-#define WG5G_GO(TP)                                                                                          \
-    do {                                                                                                     \
-        rc = msmc_allow_lds((const void*)conv_wgrad5_group_kernel<TP>, (int)lds);                            \
-        if (rc) return rc;                                                                                   \
-        MSMC_LAUNCH((conv_wgrad5_group_kernel<TP>), grid, dim3(256), lds, (msmc_stream_t)stream, a);         \
-    } while (0)
-                if (tpw == 1) WG5G_GO(1);
-                else if (tpw == 2) WG5G_GO(2);
-                else if (tpw == 3) WG5G_GO(3);
-                else if (tpw == 4) WG5G_GO(4);
-                else WG5G_GO(5);
-#undef WG5G_GO
-                msmc_conv_last = msmc_prof_name(msmc_kname("conv_wgrad5_group_kernel", nullptr, tpw, -1));
-                rc = msmc_check_launch();
-                if (rc) return rc;
-                for (int level = 0; level < 2 && nmembers; ++level) {
-                    WgReduceArgs r;
-                    r.n = 0;
-                    int rblocks = 0;
-                    for (int q = 0; q < nmembers; ++q) {
-                        const int j = members[q];
-                        const msmc_conv_desc& dj = descs[j];
-                        float* wsj = p5[j].P.ws;
-                        wg3_reduce_add(r, &rblocks, wsj, p5[j].P.ws_stride, (long)dj.ntaps * dj.Cout * dj.Cin,
-                                       (db && db[j]) ? dj.Cout : 0, (int)p5[j].gx,
-                                       wsj + (size_t)p5[j].gx * p5[j].P.ws_stride, dw[j], db ? db[j] : nullptr, level);
-                    }
-                    if (!r.n) continue;
-                    r.first[r.n] = rblocks;
-                    rc = wg3_reduce_launch(r, rblocks, stream);
-                    if (rc) return rc;
-                }
-            }
-            int nrest = 0;
-            msmc_conv_desc rest_d[MSMC_GROUP_LIMIT];
-            const void* rest_g[MSMC_GROUP_LIMIT];
-            float* rest_dw[MSMC_GROUP_LIMIT];
-            float* rest_db[MSMC_GROUP_LIMIT];
-            for (int i = 0; i < n; ++i) {
-                if (took5[i]) continue;
-                rest_d[nrest] = descs[i];
-                rest_g[nrest] = g[i];
-                rest_dw[nrest] = dw[i];
-                rest_db[nrest] = db ? db[i] : nullptr;
-                ++nrest;
-            }
-            if (!nrest) return 0;
-            return msmc_conv_wgrad_group_ws4(rest_d, rest_g, rest_dw, rest_db, nrest, wsp, ws_left * sizeof(float), stream, 1);
-        }
+    if (group4 && msmc_conv_grouping) {
+        int rc = wg_family_group_launch<Wg5Group>(descs, g, dw, db, n, took, &wsp, &ws_left, stream);
+        if (!rc) rc = wg_family_group_launch<Wg4Group>(descs, g, dw, db, n, took, &wsp, &ws_left, stream);
+        if (rc) return rc;
     }
-    if (group4 && msmc_conv_grouping && n > 1) {
-        Wg4Plan p4[MSMC_GROUP_LIMIT];
-        bool mine[MSMC_GROUP_LIMIT], took[MSMC_GROUP_LIMIT];
-        int count = 0;
-        for (int i = 0; i < n; ++i) {
-            const msmc_conv_desc* d = &descs[i];
-            const int gen = d->variant > 0 ? d->variant : msmc_wgrad_generation;
-            took[i] = false;
-            mine[i] = d->dtype == 1 && gen >= 4 && gen <= 6 && g[i] && dw[i] && d->B > 0 && d->ntaps > 0 &&
-                      d->ntaps <= MSMC_CONV_MAX_TAPS;
-            if (mine[i]) ++count;
-        }
-        if (count > 1) {
-            const int share = count < MSMC_GROUP_MAX ? count : MSMC_GROUP_MAX;
-            for (int i = 0; i < n; ++i) {
-                if (!mine[i]) continue;
-                const msmc_conv_desc* d = &descs[i];
-                const int gen = d->variant > 0 ? d->variant : msmc_wgrad_generation;
-                if (wg4_plan(d, g[i], &p4[i], gen - 4, share)) { mine[i] = false; continue; }
-                if (p4[i].ws_floats) {
-                    if (p4[i].ws_floats > ws_left) return MSMC_E_WORKSPACE;
-                    p4[i].P.ws = wsp;
-                    wsp += p4[i].ws_floats;
-                    ws_left -= p4[i].ws_floats;
-                }
-            }
-            for (int i = 0; i < n; ++i) {
-                if (!mine[i]) continue;
-                Wg4GroupArgs a;
-                a.n = 0;
-                int members[MSMC_GROUP_MAX], nmembers = 0;
-                int blocks = 0, tpw = 1;
-                size_t lds = 0;
-                for (int j = i; j < n && a.n < MSMC_GROUP_MAX; ++j) {
-                    if (!mine[j]) continue;
-                    const int k = a.n++;
-                    a.first[k] = blocks;
-                    a.nx[k] = (int)p4[j].gx;
-                    a.ny[k] = (int)p4[j].gy;
-                    a.g[k] = (const unsigned short*)g[j];
-                    a.dw[k] = dw[j];
-                    a.db[k] = db ? db[j] : nullptr;
-                    a.d[k] = descs[j];
-                    a.P[k] = p4[j].P;
-                    blocks += (int)(p4[j].gx * p4[j].gy * p4[j].gz);
-                    if (p4[j].lds > lds) lds = p4[j].lds;
-                    if (p4[j].tpw > tpw) tpw = p4[j].tpw;      // the widest member sets the accumulator budget
-                    if (p4[j].P.ws) members[nmembers++] = j;
-                    mine[j] = false;
-                    took[j] = true;
-                }
-                a.first[a.n] = blocks;
-                ++msmc_conv_launches;
-                int rc;
-                const dim3 grid((unsigned)blocks);
-#define WG4G_GO(TP)                                                                                          \
-    do {                                                                                                     \
-        rc = msmc_allow_lds((const void*)conv_wgrad4_group_kernel<TP, 1>, (int)lds);                         \
-        if (rc) return rc;                                                                                   \
-        MSMC_LAUNCH((conv_wgrad4_group_kernel<TP, 1>), grid, dim3(256), lds, (msmc_stream_t)stream, a);      \
-    } while (0)
-                if (tpw == 1) WG4G_GO(1);
-                else if (tpw == 2) WG4G_GO(2);
-                else if (tpw == 3) WG4G_GO(3);
-                else if (tpw == 4) WG4G_GO(4);
-                else WG4G_GO(5);
-#undef WG4G_GO
-                msmc_conv_last = msmc_prof_name(msmc_kname("conv_wgrad4_group_kernel", nullptr, tpw, 1));
-                rc = msmc_check_launch();
-                if (rc) return rc;
-                for (int level = 0; level < 2 && nmembers; ++level) {
-                    WgReduceArgs r;
-                    r.n = 0;
-                    int rblocks = 0;
-                    for (int q = 0; q < nmembers; ++q) {
-                        const int j = members[q];
-                        const msmc_conv_desc& dj = descs[j];
-                        float* wsj = p4[j].P.ws;
-                        wg3_reduce_add(r, &rblocks, wsj, p4[j].P.ws_stride, (long)dj.ntaps * dj.Cout * dj.Cin,
-                                       (db && db[j]) ? dj.Cout : 0, (int)p4[j].gx,
-                                       wsj + (size_t)p4[j].gx * p4[j].P.ws_stride, dw[j], db ? db[j] : nullptr, level);
-                    }
-                    if (!r.n) continue;
-                    r.first[r.n] = rblocks;
-                    rc = wg3_reduce_launch(r, rblocks, stream);
-                    if (rc) return rc;
-                }
-            }
-            // the rest of the call: everything the fourth generation did not take
-            int nrest = 0;
-            msmc_conv_desc rest_d[MSMC_GROUP_LIMIT];
-            const void* rest_g[MSMC_GROUP_LIMIT];
-            float* rest_dw[MSMC_GROUP_LIMIT];
-            float* rest_db[MSMC_GROUP_LIMIT];
-            for (int i = 0; i < n; ++i) {
-                if (took[i]) continue;
-                rest_d[nrest] = descs[i];
-                rest_g[nrest] = g[i];
-                rest_dw[nrest] = dw[i];
-                rest_db[nrest] = db ? db[i] : nullptr;
-                ++nrest;
-            }
-            if (!nrest) return 0;
-            return msmc_conv_wgrad_group_ws4(rest_d, rest_g, rest_dw, rest_db, nrest, wsp, ws_left * sizeof(float), stream, 0);
-        }
-    }
+    int left = 0;
+    for (int i = 0; i < n; ++i) left += !took[i];
     for (int i = 0; i < n; ++i) {
         const msmc_conv_desc* d = &descs[i];
         pending[i] = false;
+        if (took[i]) continue;
         const int gen = d->variant > 0 ? d->variant : msmc_wgrad_generation;
         // (fourth-generation members join a shared grid as third-generation members: the host layer times the shared
         //  grid against one launch per member, where each runs the kernel of its own choice)
-        if (!msmc_conv_grouping || d->dtype != 1 || gen == 1 || gen == 7 || gen == 8 || gen == 9 || n == 1) {
+        if (!msmc_conv_grouping || d->dtype != 1 || gen == 1 || gen == 7 || gen == 8 || gen == 9 || left == 1) {
             size_t need = msmc_conv_wgrad_workspace(d, g[i]) / sizeof(float);
             if (need > ws_left) return MSMC_E_WORKSPACE;
             int rc = msmc_conv_wgrad_ws(d, g[i], dw[i], db ? db[i] : nullptr, wsp, need * sizeof(float), stream);
@@ -3414,9 +3335,7 @@ extern "C" int msmc_conv_wgrad_group_ws4(const msmc_conv_desc* descs, const void
             ws_left -= need;
             continue;
         }
-        if (!g[i] || !dw[i] || d->B <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->QH <= 0 || d->QW <= 0 || d->ntaps <= 0 ||
-            d->ntaps > MSMC_CONV_MAX_TAPS)
-            return MSMC_E_SHAPE;
+        if (!g[i] || !dw[i] || !cv_desc_ok(d) || d->ntaps <= 0 || d->ntaps > MSMC_CONV_MAX_TAPS) return MSMC_E_SHAPE;
         int rc = wg2_plan(d, g[i], &plans[i], gen >= 3);
         if (rc) return rc;
         if (plans[i].ws_floats) {
@@ -3427,69 +3346,7 @@ extern "C" int msmc_conv_wgrad_group_ws4(const msmc_conv_desc* descs, const void
         }
         pending[i] = true;
     }
-    for (int i = 0; i < n; ++i) {
-        if (!pending[i]) continue;
-        Wg2GroupArgs a;
-        a.n = 0;
-        int members[MSMC_GROUP_MAX], nmembers = 0;            // third-generation members of this launch
-        int blocks = 0, tpw = 1;
-        size_t lds = 0;
-        for (int j = i; j < n && a.n < MSMC_GROUP_MAX; ++j) {
-            if (!pending[j]) continue;
-            const int k = a.n++;
-            a.first[k] = blocks;
-            a.nx[k] = (int)plans[j].gx;
-            a.ny[k] = (int)plans[j].gy;
-            a.g[k] = (const unsigned short*)g[j];
-            a.dw[k] = dw[j];
-            a.db[k] = db ? db[j] : nullptr;
-            a.d[k] = descs[j];
-            a.G[k] = plans[j].G;
-            a.P[k] = plans[j].P;
-            blocks += (int)(plans[j].gx * plans[j].gy * plans[j].gz);
-            if (plans[j].lds > lds) lds = plans[j].lds;
-            if (plans[j].tpw > tpw) tpw = plans[j].tpw;        // the widest member sets the accumulator budget
-            if (plans[j].P.ws) members[nmembers++] = j;
-            pending[j] = false;
-        }
-        a.first[a.n] = blocks;
-        ++msmc_conv_launches;
-        int rc;
-        const dim3 grid((unsigned)blocks);
-#define WG2G_GO(TP)                                                                                          \
-    do {                                                                                                     \
-        rc = msmc_allow_lds((const void*)conv_wgrad2_group_kernel<TP>, (int)lds);                            \
-        if (rc) return rc;                                                                                   \
-        MSMC_LAUNCH((conv_wgrad2_group_kernel<TP>), grid, dim3(256), lds, (msmc_stream_t)stream, a);          \
-    } while (0)
-        if (tpw == 1) WG2G_GO(1);
-        else if (tpw == 2) WG2G_GO(2);
-        else if (tpw == 3) WG2G_GO(3);
-        else if (tpw == 4) WG2G_GO(4);
-        else WG2G_GO(5);
-#undef WG2G_GO
-        msmc_conv_last = msmc_prof_name(msmc_kname("conv_wgrad2_group_kernel", nullptr, tpw, -1));
-        rc = msmc_check_launch();
-        if (rc) return rc;
-        for (int level = 0; level < 2 && nmembers; ++level) {
-            WgReduceArgs r;
-            r.n = 0;
-            int rblocks = 0;
-            for (int q = 0; q < nmembers; ++q) {
-                const int j = members[q];
-                const msmc_conv_desc& dj = descs[j];
-                float* wsj = plans[j].P.ws;
-                wg3_reduce_add(r, &rblocks, wsj, plans[j].P.ws_stride, (long)dj.ntaps * dj.Cout * dj.Cin,
-                               (db && db[j]) ? dj.Cout : 0, (int)plans[j].gx, wsj + (size_t)plans[j].gx * plans[j].P.ws_stride,
-                               dw[j], db ? db[j] : nullptr, level);
-            }
-            if (!r.n) continue;
-            r.first[r.n] = rblocks;
-            rc = wg3_reduce_launch(r, rblocks, stream);
-            if (rc) return rc;
-        }
-    }
-    return 0;
+    return wg_group_run<Wg2Group>(descs, g, dw, db, n, plans, pending, stream);
 }
 extern "C" int msmc_conv_wgrad_group_ws(const msmc_conv_desc* descs, const void* const* g, float* const* dw,
                                         float* const* db, int n, void* workspace, size_t workspace_bytes,

@@ -456,5 +456,28 @@ static int cv3_launch(const msmc_conv_desc* d, msmc_stream stream) {
     if (rc) return rc;
     if (!pl.applies) return 0;
     rc = cv3_dispatch(pl, dim3(pl.gx, pl.gy), pl.lds, stream, d, &pl.G, nullptr);
-    return rc ? (rc < 0 ? rc : -rc) : 1;
+    return cv_launched(rc);
 }
+
+// members of a grouped call (cv_family_group_launch): one grid per configuration (tile shape, chunk, halo registers)
+struct Cv3Family {
+    typedef Cv3Plan Plan;
+    typedef CvGroupArgs Args;
+    static constexpr int min_members = 1;
+    static constexpr bool lone_single = true;
+    static bool mine(const msmc_conv_desc* d) { return cv3_is_variant(d->variant); }
+    static int plan(const msmc_conv_desc* d, Plan* pl, int) { return cv3_plan(d, d->variant, pl); }
+    static bool same(const Plan& p, const Plan& q) {
+        return p.wm == q.wm && p.ntw == q.ntw && p.ckm == q.ckm && p.xv == q.xv && p.xdma == q.xdma;
+    }
+    static int blocks(const Plan& p) { return (int)(p.gx * p.gy); }
+    static int* head(Args& a, int m) { a.n = m; return a.first; }
+    static void fill(Args& a, int k, const msmc_conv_desc& d, const Plan& p) {
+        a.nx[k] = (int)p.gx;
+        a.d[k] = d;
+        a.G[k] = p.G;
+    }
+    static int dispatch(const Plan& p, int blocks, size_t lds, msmc_stream stream, const msmc_conv_desc* d, const Args* group) {
+        return cv3_dispatch(p, group ? dim3((unsigned)blocks) : dim3(p.gx, p.gy), lds, stream, d, &p.G, group);
+    }
+};

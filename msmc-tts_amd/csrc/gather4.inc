@@ -407,12 +407,11 @@ static int cv4_launch(const msmc_conv_desc* d, msmc_stream stream) {
     static thread_local char name[64];
     snprintf(name, sizeof(name), "%s<%d, %d>", d->variant == 33 ? "conv_gather4d_kernel" : "conv_gather4_kernel", pl.ncb, pl.ckm);
     msmc_conv_last = msmc_prof_name(name);
-    rc = msmc_check_launch();
-    return rc ? (rc < 0 ? rc : -rc) : 1;
+    return cv_launched(msmc_check_launch());
 }
 
 // Variant-32 members of a grouped call on ONE persistent grid (off by default: not yet timed on the GPU --
-// msmc_conv_set_gather4_grouping(1) turns it on for sweeps).  done[i] = member i was launched here.
+// msmc_conv_set_gather4_grouping(1) turns it on for sweeps).  done[i] is set for the members launched here.
 static int msmc_cv4_grouping = 0;
 extern "C" void msmc_conv_set_gather4_grouping(int on) { msmc_cv4_grouping = on; }
 static int cv4_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stream, bool* done) {
@@ -420,7 +419,6 @@ static int cv4_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stre
     bool mine[MSMC_GROUP_LIMIT];
     int count = 0;
     for (int i = 0; i < n; ++i) {
-        done[i] = false;
         mine[i] = false;
         if (!msmc_cv4_grouping || descs[i].variant != 32) continue;
         int rc = cv4_plan(&descs[i], &pl[i]);

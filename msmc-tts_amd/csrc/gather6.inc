@@ -319,17 +319,26 @@ static int cv6_plan(const msmc_conv_desc* d, Cv6Plan* pl, int share = 1) {
     return 0;
 }
 
-#define CV6_ONE(KERNEL_, NC_, ...)                                                                                 \
+// SINGLE (d, R) or GROUP launch of one number of output blocks
+static int cv6_dispatch(const Cv6Plan& pl, int blocks, size_t lds, msmc_stream stream, const msmc_conv_desc* d,
+                        const Cv6GroupArgs* group) {
+    int rc;
+#define CV6_GO(KERNEL_, NC_, ...)                                                                                  \
     do {                                                                                                           \
         rc = msmc_allow_lds((const void*)KERNEL_<NC_>, (int)lds);                                                  \
         if (rc) return rc;                                                                                         \
         MSMC_LAUNCH((KERNEL_<NC_>), dim3((unsigned)blocks), dim3(256), lds, (msmc_stream_t)stream, __VA_ARGS__);   \
     } while (0)
-#define CV6_GO(KERNEL_, ...)                                                                                       \
-    do {                                                                                                           \
-        if (nco == 1) CV6_ONE(KERNEL_, 1, __VA_ARGS__);                                                            \
-        else CV6_ONE(KERNEL_, 2, __VA_ARGS__);                                                                     \
-    } while (0)
+    if (!group && pl.R.nco == 1) CV6_GO(conv_gather6_kernel, 1, *d, pl.R);
+    else if (!group) CV6_GO(conv_gather6_kernel, 2, *d, pl.R);
+    else if (pl.R.nco == 1) CV6_GO(conv_gather6_group_kernel, 1, *group);
+    else CV6_GO(conv_gather6_group_kernel, 2, *group);
+#undef CV6_GO
+    static thread_local char name[64];
+    snprintf(name, sizeof(name), "%s<%d>", group ? "conv_gather6_group_kernel" : "conv_gather6_kernel", pl.R.nco);
+    msmc_conv_last = msmc_prof_name(name);
+    return msmc_check_launch();
+}
 
 // one descriptor: 1 = launched, 0 = does not apply, < 0 error
 static int cv6_launch(const msmc_conv_desc* d, msmc_stream stream) {
@@ -337,65 +346,26 @@ static int cv6_launch(const msmc_conv_desc* d, msmc_stream stream) {
     int rc = cv6_plan(d, &pl);
     if (rc) return rc;
     if (!pl.applies) return 0;
-    const int nco = pl.R.nco, blocks = pl.blocks;
-    const size_t lds = pl.lds;
-    CV6_GO(conv_gather6_kernel, *d, pl.R);
-    static thread_local char name[64];
-    snprintf(name, sizeof(name), "conv_gather6_kernel<%d>", nco);
-    msmc_conv_last = msmc_prof_name(name);
-    rc = msmc_check_launch();
-    return rc ? (rc < 0 ? rc : -rc) : 1;
+    return cv_launched(cv6_dispatch(pl, pl.blocks, pl.lds, stream, d, nullptr));
 }
 
-// members of a grouped call on the thin-channel kernel: one grid per number of output blocks (any mix of channel counts).  done[i] = launched here.
-static int cv6_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stream, bool* done) {
-    Cv6Plan p6[MSMC_GROUP_LIMIT];
-    bool todo[MSMC_GROUP_LIMIT];
-    int count = 0;
-    for (int i = 0; i < n; ++i) {
-        done[i] = todo[i] = false;
-        if (cv6_is_variant(descs[i].variant)) ++count;
+// members of a grouped call (cv_family_group_launch): one grid per number of output blocks (any mix of channel counts),
+// every member planned for its share of the chip
+struct Cv6Family {
+    typedef Cv6Plan Plan;
+    typedef Cv6GroupArgs Args;
+    static constexpr int min_members = 1;
+    static constexpr bool lone_single = true;
+    static bool mine(const msmc_conv_desc* d) { return cv6_is_variant(d->variant); }
+    static int plan(const msmc_conv_desc* d, Plan* pl, int share) { return cv6_plan(d, pl, share); }
+    static bool same(const Plan& p, const Plan& q) { return p.R.nco == q.R.nco; }
+    static int blocks(const Plan& p) { return p.blocks; }
+    static int* head(Args& a, int m) { a.n = m; return a.first; }
+    static void fill(Args& a, int k, const msmc_conv_desc& d, const Plan& p) {
+        a.d[k] = d;
+        a.R[k] = p.R;
     }
-    if (!count) return 0;
-    for (int i = 0; i < n; ++i) {
-        if (!cv6_is_variant(descs[i].variant)) continue;
-        int rc = cv6_plan(&descs[i], &p6[i], count < MSMC_GROUP_MAX ? count : MSMC_GROUP_MAX);
-        if (rc) return rc;
-        if (!p6[i].applies) return MSMC_E_SHAPE;
-        todo[i] = done[i] = true;
+    static int dispatch(const Plan& p, int blocks, size_t lds, msmc_stream stream, const msmc_conv_desc* d, const Args* group) {
+        return cv6_dispatch(p, blocks, lds, stream, d, group);
     }
-    for (int i = 0; i < n; ++i) {
-        if (!todo[i]) continue;
-        Cv6GroupArgs ga;
-        ga.n = 0;
-        int blocks = 0;
-        size_t lds = 0;
-        const int nco = p6[i].R.nco;
-        for (int j = i; j < n && ga.n < MSMC_GROUP_MAX; ++j) {
-            if (!todo[j] || p6[j].R.nco != nco) continue;
-            ga.first[ga.n] = blocks;
-            ga.d[ga.n] = descs[j];
-            ga.R[ga.n] = p6[j].R;
-            blocks += p6[j].blocks;
-            if (p6[j].lds > lds) lds = p6[j].lds;
-            todo[j] = false;
-            ++ga.n;
-        }
-        ga.first[ga.n] = blocks;
-        ++msmc_conv_launches;
-        int rc;
-        if (ga.n == 1) {
-            CV6_GO(conv_gather6_kernel, ga.d[0], ga.R[0]);
-        } else {
-            CV6_GO(conv_gather6_group_kernel, ga);
-        }
-        static thread_local char name[64];
-        snprintf(name, sizeof(name), "%s<%d>", ga.n == 1 ? "conv_gather6_kernel" : "conv_gather6_group_kernel", nco);
-        msmc_conv_last = msmc_prof_name(name);
-        rc = msmc_check_launch();
-        if (rc) return rc;
-    }
-    return 0;
-}
-#undef CV6_GO
-#undef CV6_ONE
+};

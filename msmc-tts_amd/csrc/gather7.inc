@@ -543,44 +543,27 @@ static int cv7_launch(const msmc_conv_desc* d, msmc_stream stream) {
     if (rc) return rc;
     if (!pl.applies) return 0;
     rc = cv7_dispatch(pl, (unsigned)pl.blocks, pl.lds, stream, d, nullptr);
-    return rc ? (rc < 0 ? rc : -rc) : 1;
+    return cv_launched(rc);
 }
 
-// members of a grouped call on the seventh generation: one grid per configuration.  done[i] = launched here.
-static int cv7_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stream, bool* done) {
-    Cv7Plan p7[MSMC_GROUP_LIMIT];
-    bool todo[MSMC_GROUP_LIMIT];
-    for (int i = 0; i < n; ++i) {
-        done[i] = todo[i] = false;
-        if (!cv7_is_variant(descs[i].variant)) continue;
-        int rc = cv7_plan(&descs[i], descs[i].variant, &p7[i]);
-        if (rc) return rc;
-        if (!p7[i].applies) return MSMC_E_SHAPE;
-        todo[i] = done[i] = true;
+// members of a grouped call (cv_family_group_launch): one grid per configuration
+struct Cv7Family {
+    typedef Cv7Plan Plan;
+    typedef Cv7GroupArgs Args;
+    static constexpr int min_members = 1;
+    static constexpr bool lone_single = true;
+    static bool mine(const msmc_conv_desc* d) { return cv7_is_variant(d->variant); }
+    static int plan(const msmc_conv_desc* d, Plan* pl, int) { return cv7_plan(d, d->variant, pl); }
+    static bool same(const Plan& p, const Plan& q) { return p.cfg == q.cfg; }
+    static int blocks(const Plan& p) { return p.blocks; }
+    static int* head(Args& ga, int m) { ga.a.n = m; return ga.a.first; }
+    static void fill(Args& ga, int k, const msmc_conv_desc& d, const Plan& p) {
+        ga.a.nx[k] = p.blocks;
+        ga.a.d[k] = d;
+        ga.a.G[k] = p.G;
+        ga.R[k] = Cv7Run{p.tilesM, p.tilesN};
     }
-    for (int i = 0; i < n; ++i) {
-        if (!todo[i]) continue;
-        Cv7GroupArgs ga;
-        ga.a.n = 0;
-        int blocks = 0;
-        size_t lds = 0;
-        for (int j = i; j < n && ga.a.n < MSMC_GROUP_MAX; ++j) {
-            if (!todo[j] || p7[j].cfg != p7[i].cfg) continue;
-            ga.a.first[ga.a.n] = blocks;
-            ga.a.nx[ga.a.n] = p7[j].blocks;
-            ga.a.d[ga.a.n] = descs[j];
-            ga.a.G[ga.a.n] = p7[j].G;
-            ga.R[ga.a.n] = Cv7Run{p7[j].tilesM, p7[j].tilesN};
-            blocks += p7[j].blocks;
-            if (p7[j].lds > lds) lds = p7[j].lds;
-            todo[j] = false;
-            ++ga.a.n;
-        }
-        ga.a.first[ga.a.n] = blocks;
-        ++msmc_conv_launches;
-        int rc = ga.a.n == 1 ? cv7_dispatch(p7[i], (unsigned)p7[i].blocks, p7[i].lds, stream, &ga.a.d[0], nullptr)
-                             : cv7_dispatch(p7[i], (unsigned)blocks, lds, stream, nullptr, &ga);
-        if (rc) return rc;
+    static int dispatch(const Plan& p, int blocks, size_t lds, msmc_stream stream, const msmc_conv_desc* d, const Args* group) {
+        return cv7_dispatch(p, (unsigned)blocks, lds, stream, d, group);
     }
-    return 0;
-}
+};

@@ -402,15 +402,14 @@ static int g1_launch(const msmc_conv_desc* d, msmc_stream stream) {
     else G1_GO(unsigned short, 2, "conv_gemm1_kernel<unsigned short, 2>");
 #undef G1_GO
 #undef G1S_GO
-    const int rc = msmc_check_launch();
-    return rc ? (rc < 0 ? rc : -rc) : 1;
+    return cv_launched(msmc_check_launch());
 }
 
 
-// plan of one split-form member (the checks of g1_launch): 1 = takes it
-struct G1sPlan { Gemm1Params P; int mw; unsigned blocks; size_t lds; };
+// plan of one split-form member (the checks of g1_launch)
+struct G1sPlan { int applies; Gemm1Params P; int mw; unsigned blocks; size_t lds; };
 static int g1s_plan(const msmc_conv_desc* d, G1sPlan* pl) {
-    if (d->variant != 36 && d->variant != 37) return 0;
+    pl->applies = 0;
     if (d->dtype != 0 || d->ntaps != 1 || d->tap_dy[0] != 0 || d->tap_dx[0] != 0) return 0;
     if (d->QH != d->Hout || d->QW != d->Wout || d->Hout != d->Hin || d->Wout != d->Win) return 0;
     if (d->oy0 || d->ox0 || d->iy0 || d->ix0 || d->osy != 1 || d->osx != 1 || d->isy != 1 || d->isx != 1) return 0;
@@ -431,56 +430,39 @@ static int g1s_plan(const msmc_conv_desc* d, G1sPlan* pl) {
     const int stages = P.nchunks < G1_STAGES ? P.nchunks : G1_STAGES;
     pl->lds = (size_t)stages * (tm_ + G1_TN) * 128;
     pl->blocks = (unsigned)(groups * 8 * (P.by_channel ? P.tilesM : P.tilesN));
-    return 1;
+    pl->applies = 1;
+    return 0;
 }
-// split-form members of a grouped call: one grid per tile width.  done[i] = launched here (a lone member keeps its own launch).
-static int g1s_group_launch(const msmc_conv_desc* descs, int n, msmc_stream stream, bool* done) {
-    G1sPlan pl[MSMC_GROUP_LIMIT];
-    bool todo[MSMC_GROUP_LIMIT];
-    int count = 0;
-    for (int i = 0; i < n; ++i) {
-        done[i] = false;
-        todo[i] = g1s_plan(&descs[i], &pl[i]) == 1;
-        count += todo[i];
+// split-form members of a grouped call (cv_family_group_launch): one grid per tile width; a member without company of its
+// width keeps its own launch (g1_launch)
+struct G1sFamily {
+    typedef G1sPlan Plan;
+    typedef G1GroupArgs Args;
+    static_assert(G1G_MAX == MSMC_GROUP_MAX, "one bucket size for every family");
+    static constexpr int min_members = 2;
+    static constexpr bool lone_single = false;
+    static bool mine(const msmc_conv_desc* d) { return d->variant == 36 || d->variant == 37; }
+    static int plan(const msmc_conv_desc* d, Plan* pl, int) { return g1s_plan(d, pl); }
+    static bool same(const Plan& p, const Plan& q) { return p.mw == q.mw; }
+    static int blocks(const Plan& p) { return (int)p.blocks; }
+    static int* head(Args& a, int m) { a.n = m; return a.first; }
+    static void fill(Args& a, int k, const msmc_conv_desc& d, const Plan& p) {
+        a.d[k] = d;
+        a.P[k] = p.P;
     }
-    if (count < 2) return 0;
-    for (int i = 0; i < n; ++i) {
-        if (!todo[i]) continue;
-        G1GroupArgs a;
-        a.n = 0;
-        int blocks = 0;
-        size_t lds = 0;
-        for (int j = i; j < n && a.n < G1G_MAX; ++j) {
-            if (!todo[j] || pl[j].mw != pl[i].mw) continue;
-            a.first[a.n] = blocks;
-            a.d[a.n] = descs[j];
-            a.P[a.n] = pl[j].P;
-            blocks += (int)pl[j].blocks;
-            if (pl[j].lds > lds) lds = pl[j].lds;
-            todo[j] = false;
-            done[j] = true;
-            ++a.n;
-        }
-        a.first[a.n] = blocks;
-        if (a.n == 1) {                                           // (no company of its width: the single launch)
-            done[i] = false;
-            continue;
-        }
-        ++msmc_conv_launches;
+    static int dispatch(const Plan& p, int blocks, size_t lds, msmc_stream stream, const msmc_conv_desc*, const Args* group) {
         int rc;
-        if (pl[i].mw == 4) {
+        if (p.mw == 4) {
             rc = msmc_allow_lds((const void*)conv_gemm1s_group_kernel<4>, (int)lds);
             if (rc) return rc;
-            MSMC_LAUNCH((conv_gemm1s_group_kernel<4>), dim3((unsigned)blocks), dim3(1024), lds, (msmc_stream_t)stream, a);
+            MSMC_LAUNCH((conv_gemm1s_group_kernel<4>), dim3((unsigned)blocks), dim3(1024), lds, (msmc_stream_t)stream, *group);
             msmc_conv_last = msmc_prof_name("conv_gemm1s_group_kernel<4>");
         } else {
             rc = msmc_allow_lds((const void*)conv_gemm1s_group_kernel<2>, (int)lds);
             if (rc) return rc;
-            MSMC_LAUNCH((conv_gemm1s_group_kernel<2>), dim3((unsigned)blocks), dim3(512), lds, (msmc_stream_t)stream, a);
+            MSMC_LAUNCH((conv_gemm1s_group_kernel<2>), dim3((unsigned)blocks), dim3(512), lds, (msmc_stream_t)stream, *group);
             msmc_conv_last = msmc_prof_name("conv_gemm1s_group_kernel<2>");
         }
-        rc = msmc_check_launch();
-        if (rc) return rc;
+        return msmc_check_launch();
     }
-    return 0;
-}
+};

@@ -204,3 +204,134 @@ def check_conv_case(case, dtype, tol, dev, parts=('fwd', 'dgrad', 'wgrad'), batc
         assert (dbR.sum(0) - bref).abs().max().item() < 1e-5 * bscale + 1e-6, 'bias grad copies'
         cs = conv.colsum(gc.reshape(-1, Cout))
         assert (cs - bref).abs().max().item() < 1e-5 * bscale + 1e-6, ('bias grad', cs, bref)
+
+
+# ---- grouped entry points with members of several kernel families in one call ---------------------------------------
+# Launch count and launch log (kernel names in launch order) of the two calls below.  Both were recorded by running
+# check_mixed_family_groups against the library built from the commit BEFORE the grouped launchers were unified into one
+# routine per direction (that commit's kernel interpreter); they hold unchanged on the interpreter and on the device.
+MIXED_FORWARD_LAUNCHES = 7
+MIXED_FORWARD_KERNELS = ['conv_gather3_group_kernel<2, 1, 1, 3, false>', 'conv_gather3_kernel<4, 1, 1, 6, false>',
+                         'conv_gather5_group_kernel<1, 1, 4, 1, 3>', 'conv_gather5_kernel<1, 1, 4, 1, 3>',
+                         'conv_gather7_group_kernel<2, 2, 2, 1, 3>', 'conv_gather6_group_kernel<2>',
+                         'conv_gather_ks_group_kernel<unsigned short, 2, 2>']
+MIXED_WGRAD_LAUNCHES = 6
+MIXED_WGRAD_KERNELS = ['conv_wgrad5_group_kernel<5>', 'conv_wgrad_reduce_kernel', 'conv_wgrad4_group_kernel<4, 1>',
+                       'conv_wgrad_reduce_kernel', 'conv_wgrad2_group_kernel<5>', 'conv_wgrad_reduce_kernel']
+
+
+def _launch_log(L, fn, device):
+    """(launch-count delta, kernel names in launch order) of fn()"""
+    import ctypes
+    L.msmc_prof_enable(1)
+    n0 = L.msmc_conv_launch_count()
+    try:
+        fn()
+        count = L.msmc_conv_launch_count() - n0
+        if torch.device(device).type == 'cuda':
+            torch.cuda.synchronize()
+        buf, ms, names = ctypes.create_string_buffer(128), ctypes.c_float(), []
+        for i in range(L.msmc_prof_count()):
+            assert L.msmc_prof_read(i, buf, 128, ctypes.byref(ms)) == 0
+            names.append(buf.value.decode())
+    finally:
+        L.msmc_prof_enable(0)
+    return count, names
+
+
+def check_mixed_family_groups(device, report=None):
+    """One msmc_conv_gather_group call and one msmc_conv_wgrad_group_ws4(group4 = 1) call whose members belong to several
+    kernel families, interleaved: every member's result is the single launch of the same descriptor bit for bit, and the
+    launches are the ones listed above, in that order.  ``report``: called with the four observed figures before they are
+    compared (recording)."""
+    import ctypes
+    from msmctts_amd.hip import conv, lib
+    L = lib.get()
+    torch.manual_seed(0)
+
+    def bf(*shape):
+        return torch.randn(*shape, device=device).bfloat16()
+
+    # ---- forward: seven gen-5 members of one configuration (more than one launch carries: six on one grid, the seventh
+    # alone), two gen-7, gen-3 members of two configurations (two + one), two thin-channel and two wave-split members
+    x5, w5, b5 = bf(2, 1, 150, 128), (bf(3, 264, 128) / 20), torch.randn(264, device=device)
+    x3, w3 = bf(2, 1, 150, 64), (bf(3, 64, 64) / 14)
+    x6, w6, b6 = bf(2, 11, 30, 16), (bf(9, 40, 16) / 12), torch.randn(40, device=device)
+    x9 = bf(2, 1, 70, 512)
+    w9 = {64: bf(3, 64, 512) / 39, 72: bf(3, 72, 512) / 39}
+
+    def g5():
+        return dict(x=x5, w=w5, geom=conv.Geometry(1, 150, (1, 3), (1, 1), (1, 2), (0, 2), False), bias=b5, in_slope=0.1)
+
+    def g3():
+        return dict(x=x3, w=w3, geom=conv.Geometry(1, 150, (1, 3), (1, 1), (1, 1), (0, 1), False), in_slope=0.1)
+
+    def g6():
+        return dict(x=x6, w=w6, geom=conv.Geometry(11, 30, (3, 3), (1, 1), (1, 1), (1, 1), False), bias=b6, out_slope=0.2)
+
+    def g9(co):
+        return dict(x=x9, w=w9[co], geom=conv.Geometry(1, 70, (1, 3), (1, 1), (1, 1), (0, 1), False), in_slope=0.1)
+
+    members = [(40, g5()), (16, g3()), (56, g5()), (40, g5()), (9, g9(64)), (50, g6()), (40, g5()), (17, g3()), (40, g5()),
+               (56, g5()), (16, g3()), (40, g5()), (9, g9(72)), (40, g5()), (50, g6()), (40, g5())]
+    st = lib.stream(x5)
+    descs, outs, refs = [], [], []
+    for variant, item in members:
+        d, out = conv._forward_desc(**item)
+        d.variant = variant
+        assert L.msmc_conv_gather(ctypes.byref(d), st) == 0, variant
+        descs.append(d); outs.append(out); refs.append(out.clone())
+        out.zero_()
+    arr = (lib.ConvDesc * len(descs))(*descs)
+    fwd = _launch_log(L, lambda: lib.check(L.msmc_conv_gather_group(arr, len(descs), st), 'msmc_conv_gather_group'), device)
+    for (variant, _), out, ref in zip(members, outs, refs):
+        assert ref.float().abs().max() > 0 and torch.equal(out, ref), variant
+
+    # ---- weight gradient: two variant-7 members, two variant-4 and one variant-5 member (one fourth-generation grid), a
+    # variant-3 member and a member outside the fourth generation's scope (Cout % 64: third generation)
+    L.msmc_conv_set_wgrad_split(2)                              # (a shared grid plans another split: fix it for bit equality)
+    try:
+        xa = bf(2, 1, 90, 64)
+        wmembers = []                                           # (H, W, kernel, stride, dilation, padding, reflect, Cout, variant)
+        wmembers.append((1, 90, (1, 3), (1, 1), (1, 1), (0, 1), False, 64, 4))
+        wmembers.append((40, 3, (5, 1), (3, 1), (1, 1), (2, 0), False, 64, 7))
+        wmembers.append((9, 20, (3, 3), (1, 2), (1, 1), (1, 1), True, 64, 3))
+        wmembers.append((1, 90, (1, 11), (1, 1), (1, 1), (0, 5), False, 64, 5))
+        wmembers.append((13, 18, (3, 3), (2, 2), (1, 1), (1, 1), True, 128, 7))
+        wmembers.append((1, 90, (1, 3), (1, 1), (1, 1), (0, 1), False, 40, 3))
+        wmembers.append((1, 90, (1, 7), (1, 1), (1, 3), (0, 9), False, 128, 4))
+        descs, keep, refs, outs = [], [], [], []
+        for (H, W, k, s, dil, pad, reflect, cout, variant) in wmembers:
+            geom = conv.Geometry(H, W, k, s, dil, pad, reflect)
+            x = xa if (H, W) == (1, 90) else bf(2, H, W, 64)
+            g = bf(2, geom.Hout, geom.Wout, cout)
+            d = conv._build_desc(x.dtype, 2, H, W, 64, geom.Hout, geom.Wout, cout, geom.fwd_lattice, geom.fwd_taps,
+                                 1 if reflect else 0, 0.1, 1.0, 1.0, 1.0)
+            d.x = d.w = d.out = x.data_ptr()
+            d.variant, d.dw_copies = variant, 1
+            T = k[0] * k[1]
+            need = L.msmc_conv_wgrad_workspace(ctypes.byref(d), g.data_ptr())
+            ws = torch.zeros(max(1, need // 4), device=device)
+            dw_ref, db_ref = torch.zeros(T, cout, 64, device=device), torch.zeros(cout, device=device)
+            assert L.msmc_conv_wgrad_ws(ctypes.byref(d), g.data_ptr(), dw_ref.data_ptr(), db_ref.data_ptr(), ws.data_ptr(),
+                                        need, st) == 0, variant
+            descs.append(d); keep.append((x, g)); refs.append((dw_ref, db_ref))
+            outs.append((torch.zeros(T, cout, 64, device=device), torch.zeros(cout, device=device)))
+        n = len(descs)
+        arr = (lib.ConvDesc * n)(*descs)
+        vp = ctypes.c_void_p * n
+        need = sum(L.msmc_conv_wgrad_workspace(ctypes.byref(d), xg[1].data_ptr()) for d, xg in zip(descs, keep))
+        ws = torch.zeros(max(1, need // 4), device=device)
+        wg = _launch_log(L, lambda: lib.check(L.msmc_conv_wgrad_group_ws4(
+            arr, vp(*[xg[1].data_ptr() for xg in keep]), vp(*[o[0].data_ptr() for o in outs]),
+            vp(*[o[1].data_ptr() for o in outs]), n, ws.data_ptr(), need, st, 1), 'msmc_conv_wgrad_group_ws4'), device)
+        for m, (dw_ref, db_ref), (dw, db) in zip(wmembers, refs, outs):
+            assert dw_ref.abs().max() > 0 and torch.equal(dw, dw_ref) and torch.equal(db, db_ref), m
+    finally:
+        L.msmc_conv_set_wgrad_split(0)
+    if report:
+        report(fwd[0], fwd[1], wg[0], wg[1])
+    assert fwd[0] == MIXED_FORWARD_LAUNCHES, fwd
+    assert fwd[1] == MIXED_FORWARD_KERNELS, fwd
+    assert wg[0] == MIXED_WGRAD_LAUNCHES, wg
+    assert wg[1] == MIXED_WGRAD_KERNELS, wg

@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
 
-from _convcases import CONVS, SMALL, check_conv_case, cl, conv_part_errors, nchw, rel
+from _convcases import CONVS, SMALL, check_conv_case, check_mixed_family_groups, cl, conv_part_errors, nchw, rel
 
 
 @pytest.mark.parametrize('dtype,tol', [(torch.float32, 2e-4), (torch.bfloat16, 2e-2)])
@@ -23,6 +23,12 @@ def test_conv_small_and_thin_shapes(case):
     """odd / thin channel counts, ragged tiles; offset (not 16-byte aligned) operands are refused"""
     check_conv_case(case, torch.bfloat16, 2e-2, DEV, batch_offset=1)
     check_conv_case(case, torch.float32, 2e-4, DEV)
+
+
+def test_grouped_calls_with_members_of_several_kernel_families():
+    """the members of tests/test_product_emu.py's test of the same name on the device: bit-equal to single launches, the same
+    launch count and launch log"""
+    check_mixed_family_groups(DEV)
 
 
 @pytest.mark.parametrize('gen', [1, 2, 3])

@@ -508,6 +508,13 @@ def test_wgrad_general_lattice_dma_staging():
         L.msmc_conv_set_wgrad_split(0)
 
 
+def test_grouped_calls_with_members_of_several_kernel_families():
+    """msmc_conv_gather_group and msmc_conv_wgrad_group_ws4 with the members of five forward families and of every grouped
+    weight-gradient generation interleaved in one call: results of single launches bit for bit, launch count and launch log
+    as recorded (_convcases.check_mixed_family_groups)"""
+    _convcases.check_mixed_family_groups('cpu')
+
+
 def test_wgrad_fourth_generation_grouped():
     """msmc_conv_wgrad_group_ws4(group4 = 1): the fourth-generation members of a grouped call share one grid of their own
     kernel (members of different tap counts: the widest sets the accumulator budget), a member outside the scope goes the
