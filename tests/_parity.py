@@ -832,6 +832,230 @@ def check_attention(dev):
             close(out[1].float().reshape(T, H, 64), x[1, :1, :, 128:].expand(T, H, 64), 1e-2, what='single key')
 
 
+# csrc/attn.hip where a wave streams over MORE than one tile (T > 128): the register prefetch of the next tile, the
+# running-max rescale and the merge of four partial softmaxes, in the forward kernel and both backward kernels.
+ATTN_SCALE = 0.125
+ATTN_TILE_CASES = (               # tag, B, T, H, gain (on the q and k channels), valid keys per utterance, p_drop
+    ('flat', 2, 161, 2, 0.7, (161, 130), 0.0),      # second tile for wave 0 only; ragged last tile; tile 4 half masked in row 1
+    ('peaked', 2, 161, 2, 2.0, (161, 130), 0.0),    # the same, mean of the largest probability per query about 0.55
+    ('one-hot', 2, 161, 2, 4.0, (161, 130), 0.0),   # near one-hot softmax: the running maximum changes tile to tile
+    ('T=128', 2, 128, 1, 2.0, (128, 127), 0.0),     # exactly one tile per wave: k0 + kstep < T false on the boundary
+    ('T=289 drop', 1, 289, 1, 3.0, (289,), 0.1),    # 3 tiles for wave 0, 2 for the others, ONE valid key in the last tile
+    ('drop .25', 2, 161, 2, 2.0, (161, 130), 0.25),  # dropout across tiles in all three kernels
+    ('4 heads', 3, 97, 4, 2.0, (97, 1, 33), 0.0),   # a one-key utterance; waves 1-3 fully masked for one row, busy for others
+    ('T=1', 1, 1, 1, 1.0, (1,), 0.0),               # a single frame: dq and dk are identically zero
+    ('planted', 1, 289, 1, 2.0, (289,), 0.0),       # query 5's best key is 270 (wave 0's THIRD tile): its maximum moves up late
+)
+ATTN_PLANT = (5, 270, 0.75)       # query, key, factor: k[270] = 0.75 * q[5]  (case 'planted')
+
+
+def _attn_inputs(tag, B, T, H, gain, lens, seed):
+    """bf16 projection [B, T, H*192], bf16 output gradient [B, T, H*64], positions [B, T] (0 = padding); drawn on the CPU
+    so that the interpreter and the GPU see the same values"""
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, T, H, 192, generator=gen)
+    x[..., :128] *= gain
+    if tag == 'planted':
+        q, k, f = ATTN_PLANT
+        x[0, k, 0, 64:128] = f * x[0, q, 0, :64]
+    go = torch.randn(B, T, H * 64, generator=gen).bfloat16()
+    pos = torch.zeros(B, T, dtype=torch.long)
+    for b, n in enumerate(lens):
+        pos[b, :n] = torch.arange(1, n + 1)
+    return x.reshape(B, T, H * 192).bfloat16(), go, pos
+
+
+def _attn_run(dev, qkv, go, pos, H, p_drop=0.0, salt=0):
+    """forward and backward on the kernels -> out [B, T, H*64], qkv.grad [B, T, H*192] (bf16, on the CPU)"""
+    from msmctts_amd.hip import attn
+    x = qkv.detach().clone().to(dev).requires_grad_(True)
+    out = attn.attention(x, attn.pad_key_bias(pos.to(dev)), H, ATTN_SCALE, p_drop, salt)
+    out.backward(go.to(dev))
+    return out.detach().cpu(), x.grad.cpu()
+
+
+def _attn_heads(out, grad, H):
+    """kernel results in fp64 as [B, H, T, 64] each"""
+    B, T, _ = out.shape
+    g = grad.double().reshape(B, T, H, 192).permute(0, 2, 1, 3)
+    return {'out': out.double().reshape(B, T, H, 64).permute(0, 2, 1, 3), 'dq': g[..., :64], 'dk': g[..., 64:128],
+            'dv': g[..., 128:]}
+
+
+def _attn_keep_mask(dev, B, T, H, p_drop, salt):
+    """the kernel's own keep mask [B, H, T, T] for (seed word, salt): ceil(T / 64) probe calls with zero q and k (uniform
+    probabilities) and one-hot values on keys 64 c .. 64 c + 63 -- output channel j of call c is keep(q, 64 c + j) / (T (1-p))"""
+    from msmctts_amd.hip import attn
+    flat = attn.pad_key_bias(torch.ones(B, T, dtype=torch.long, device=dev))
+    mask = torch.zeros(B, H, T, T)
+    for c in range((T + 63) // 64):
+        n = min(64, T - 64 * c)
+        probe = torch.zeros(B, T, H, 192)
+        for j in range(n):
+            probe[:, 64 * c + j, :, 128 + j] = 1.0
+        o = attn.attention(probe.reshape(B, T, H * 192).bfloat16().to(dev), flat, H, 0.0, p_drop, salt)
+        mask[..., 64 * c:64 * c + n] = (o.float().cpu().reshape(B, T, H, 64)[..., :n].permute(0, 2, 1, 3) > 0).float()
+    return mask
+
+
+def _attn_chain(qkv, go, pos, H, mask, p_drop, rnd):
+    """the attention chain and its gradients in fp64 from the bf16 values, [B, H, T, *]; ``rnd`` is applied wherever the
+    kernels store bf16 (P * M as the operand of the second product, O -- also the O that feeds D --, dS, the four results)"""
+    B, T, _ = qkv.shape
+    x = qkv.double().reshape(B, T, H, 192).permute(0, 2, 1, 3)
+    q, k, v = x[..., :64], x[..., 64:128], x[..., 128:]
+    do = go.double().reshape(B, T, H, 64).permute(0, 2, 1, 3)
+    bias = torch.zeros(B, T, dtype=torch.float64).masked_fill_(pos.eq(0), float('-inf'))
+    p = torch.softmax(ATTN_SCALE * (q @ k.transpose(-1, -2)) + bias[:, None, None, :], -1)
+    m = mask.double() / (1 - p_drop)
+    pm = rnd(p * m)
+    o = rnd(pm @ v)
+    d = (do * o).sum(-1, keepdim=True)
+    ds = rnd(p * (m * (do @ v.transpose(-1, -2)) - d))
+    return {'out': o, 'dq': rnd(ATTN_SCALE * (ds @ k)), 'dk': rnd(ATTN_SCALE * (ds.transpose(-1, -2) @ q)),
+            'dv': rnd(pm.transpose(-1, -2) @ do), 'p': p, 'do': do}
+
+
+def _attn_yardstick_bounds(tag, got, exact, yard, lens, l2_margin=1.5, max_margin=2.0):
+    """kernel error against the yardstick's (both measured from the exact chain) per quantity; the utterances with ONE
+    valid key, whose dq and dk are identically zero, are held to 2^-8 of the output gradient instead"""
+    one_key = [b for b, n in enumerate(lens) if n == 1]
+    rest = [b for b, n in enumerate(lens) if n != 1]
+    line, failed = [], []
+    for name in ('out', 'dq', 'dk', 'dv'):
+        rows = rest if name in ('dq', 'dk') else list(range(len(lens)))
+        if name in ('dq', 'dk'):
+            for b in one_key:
+                assert float(exact[name][b].abs().max()) <= 1e-12, (tag, name, b)      # zero but for fp64 rounding
+                zero_err, bound = float(got[name][b].abs().max()), 2.0 ** -8 * float(exact['do'][b].abs().max())
+                line.append('%s[%d] zero: %.2e (bound %.2e)' % (name, b, zero_err, bound))
+                if not zero_err <= bound:
+                    failed.append('%s[%d] max %.3e > %.3e' % (name, b, zero_err, bound))
+        if not rows:
+            continue
+        ek, ey, ref = got[name][rows] - exact[name][rows], yard[name][rows] - exact[name][rows], exact[name][rows]
+        norm = float(ref.norm())
+        l2k, l2y, mxk, mxy = float(ek.norm()) / norm, float(ey.norm()) / norm, float(ek.abs().max()), float(ey.abs().max())
+        line.append('%s l2 %.2e / %.2e = %s  max %.2e / %.2e = %s' % (
+            name, l2k, l2y, '%.2f' % (l2k / l2y) if l2y else '-', mxk, mxy, '%.2f' % (mxk / mxy) if mxy else '-'))
+        if not l2k <= l2_margin * l2y:
+            failed.append('%s rel-L2 %.3e > %.1f x %.3e' % (name, l2k, l2_margin, l2y))
+        if not mxk <= max_margin * mxy:
+            failed.append('%s max-abs %.3e > %.1f x %.3e' % (name, mxk, max_margin, mxy))
+    print('attention tiles %-10s (kernel / yardstick): %s' % (tag, ' | '.join(line)))
+    assert not failed, (tag, failed)
+
+
+def check_attention_tiles(dev):
+    """csrc/attn.hip at sizes where a wave streams over more than one 32-key (32-query) tile, against the chain
+
+        S = scale Q K^T + bias, P = softmax(S), M = mask / (1 - p), O = (P * M) V, D = rowsum(dO * O),
+        dS = P * (M * (dO V^T) - D), dQ = scale dS K, dK = scale dS^T Q, dV = (P * M)^T dO
+
+    in fp64 from the same bf16 values of qkv and dO.  The yardstick is the same fp64 chain with a bf16 round trip wherever
+    the kernels store bf16 (P * M, O, dS, the four results); its distance from the exact chain is what bf16 storage alone
+    costs.  For out, dq, dk, dv of every case: the kernel's relative L2 error <= 1.5 x the yardstick's and its largest
+    error <= 2 x the yardstick's -- the margin is for what the yardstick leaves out (fp32 accumulation, the order of the sum
+    over four waves, the hardware's exp, exp(s - m) rounded before instead of after the normalisation).  With dropout the
+    mask M is the kernel's own, recovered over ALL keys by probe calls (_attn_keep_mask); the gradient bounds then hold only
+    if both backward kernels regenerated exactly that mask.  The mask itself: keep rate within 4 sigma of a binomial,
+    the same for the same salt, another for another salt, another for another (batch, head).
+
+    Measured kernel / yardstick ratios on the kernel interpreter, relative L2 | max-abs ('-': both errors are zero;
+    dq and dk of the one-key utterance of '4 heads' came to 1.4e-6 and 3.4e-6 against a bound of 1.8e-2):
+
+        case          out           dq            dk            dv
+        flat          0.95 | 0.94   1.00 | 1.00   1.00 | 1.00   1.00 | 1.00
+        peaked        0.75 | 0.68   0.82 | 0.66   0.83 | 0.67   1.00 | 1.00
+        one-hot       0.81 | 0.65   0.83 | 0.74   0.82 | 0.75   1.00 | 1.00
+        T=128         0.73 | 0.68   0.72 | 0.68   0.74 | 0.62   1.00 | 1.00
+        T=289 drop    0.98 | 0.74   1.03 | 0.89   1.03 | 0.91   1.00 | 1.00
+        drop .25      1.04 | 1.37   0.96 | 0.76   0.95 | 0.67   1.00 | 1.00
+        4 heads       0.77 | 0.63   0.81 | 0.80   0.81 | 0.83   1.00 | 1.00
+        T=1           -    | -      zero          zero          -    | -
+        planted       0.76 | 0.65   0.78 | 0.62   0.81 | 0.97   1.00 | 1.00
+
+    (The same table from the gfx950 library is still to be recorded: the check prints it, one line per case.)"""
+    from msmctts_amd.hip import norm
+    for n, (tag, B, T, H, gain, lens, pd) in enumerate(ATTN_TILE_CASES):
+        qkv, go, pos = _attn_inputs(tag, B, T, H, gain, lens, seed=100 + n)
+        salt = norm.new_salt()
+        mask = torch.ones(B, H, T, T)
+        if pd > 0:
+            mask = _attn_keep_mask(dev, B, T, H, pd, salt)
+            sigma = (pd * (1 - pd) / mask.numel()) ** 0.5
+            assert abs(mask.mean().item() - (1 - pd)) <= 4 * sigma, (tag, mask.mean().item(), sigma)
+            assert torch.equal(mask, _attn_keep_mask(dev, B, T, H, pd, salt)), tag
+            assert not torch.equal(mask, _attn_keep_mask(dev, B, T, H, pd, norm.new_salt())), tag
+            flat = mask.reshape(B * H, T, T)
+            assert all(not torch.equal(flat[0], flat[j]) for j in range(1, B * H)), tag      # (the hash takes b * H + h)
+        exact = _attn_chain(qkv, go, pos, H, mask, pd, lambda x: x)
+        if tag == 'planted':
+            q, k, _ = ATTN_PLANT
+            assert int(exact['p'][0, 0, q].argmax()) == k and float(exact['p'][0, 0, q, :32].sum()) < 1e-3
+        yard = _attn_chain(qkv, go, pos, H, mask, pd, lambda x: x.bfloat16().double())
+        got = _attn_heads(*_attn_run(dev, qkv, go, pos, H, pd, salt), H)
+        _attn_yardstick_bounds(tag, got, exact, yard, lens)
+
+
+def check_attention_exact_properties(dev):
+    """csrc/attn.hip without dropout, bit for bit: an utterance gives the same output rows alone (T = 140) and embedded in a
+    longer padded batch row (T = 300, random data behind it: masked tiles add p = 0 with corr = 1 and the valid tiles stay
+    with their waves); a batch row gives the same output and gradient alone and among others (a workgroup depends on b
+    through base addresses only); two identical calls give identical results (no atomics, fixed merge order)."""
+    H = 2
+    qkv, go, pos = _attn_inputs('pad', 1, 300, H, 2.0, (140,), seed=200)
+    long_out, _ = _attn_run(dev, qkv, go, pos, H)
+    short_out, _ = _attn_run(dev, qkv[:, :140].contiguous(), go[:, :140].contiguous(), pos[:, :140].contiguous(), H)
+    assert bool(qkv[:, 140:].float().abs().max() > 1) and torch.equal(long_out[:, :140], short_out)
+    qkv, go, pos = _attn_inputs('batch', 3, 161, H, 2.0, (161, 130, 40), seed=201)
+    out, grad = _attn_run(dev, qkv, go, pos, H)
+    again = _attn_run(dev, qkv, go, pos, H)
+    assert torch.equal(out, again[0]) and torch.equal(grad, again[1])
+    for b in range(3):
+        o1, g1 = _attn_run(dev, qkv[b:b + 1], go[b:b + 1], pos[b:b + 1], H)
+        assert torch.equal(out[b:b + 1], o1), ('out', b)
+        assert torch.equal(grad[b:b + 1], g1), ('qkv.grad', b)
+
+
+def check_attention_wrapper(dev):
+    """msmctts_amd/hip/attn.py: an fp32 and a non-contiguous output gradient give the gradient of the bf16 contiguous one
+    (through autograd and handed to the backward function directly); arguments the kernels do not support come back from
+    the C entry points as the shape error (nothing is launched) and are raised"""
+    from msmctts_amd.hip import attn, lib
+    B, T, H = 2, 45, 2
+    qkv, go, pos = _attn_inputs('wrapper', B, T, H, 1.0, (45, 32), seed=300)
+    bias = attn.pad_key_bias(pos.to(dev))
+    strided = go.transpose(1, 2).contiguous().transpose(1, 2)
+    assert not strided.is_contiguous() and torch.equal(strided, go)
+    _, want = _attn_run(dev, qkv, go, pos, H)
+    for g in (go.float(), strided, strided.float()):
+        x = qkv.clone().to(dev).requires_grad_(True)
+        out = attn.attention(x, bias, H, ATTN_SCALE)
+        direct = out.grad_fn.apply(g.to(dev))[0]                  # (the engine would cast a root gradient to bf16 itself)
+        assert torch.equal(direct.cpu(), want), (g.dtype, g.is_contiguous())
+        out.backward(g.to(dev))
+        assert torch.equal(x.grad.cpu(), want), (g.dtype, g.is_contiguous())
+    x, g, dx = qkv.to(dev), go.to(dev), torch.empty_like(qkv, device=dev)
+    for bad_bias, pd in ((bias[:, :T].contiguous(), 0.0),                                   # Tp % 32 != 0
+                         (bias, 1.0),                                                       # nothing would be kept
+                         (bias[:, :32].contiguous(), 0.0)):                                 # Tp < T
+        with pytest_raises(RuntimeError) as err:
+            attn.attention(x, bad_bias, H, ATTN_SCALE, pd, 1)
+        assert 'msmc_attn_fwd failed with code -2' in str(err.value)
+        out, lse, dsum = torch.empty(B, T, H * 64, dtype=torch.bfloat16, device=dev), torch.empty(B * H, T, device=dev), \
+            torch.empty(B * H, T, device=dev)
+        seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        rc = lib.get().msmc_attn_bwd(lib.ptr(x), lib.ptr(bad_bias), lib.ptr(out), lib.ptr(lse), lib.ptr(g), lib.ptr(dx), lib.ptr(dsum), B, T, H, bad_bias.shape[1], ATTN_SCALE, pd,
+                                     lib.ptr(seed), 1, lib.stream(x))
+        assert rc == -2, rc
+    out = attn.attention(x.clone().requires_grad_(True), bias, H, ATTN_SCALE)          # ... and raised by the backward wrapper too
+    out.grad_fn.args = (H, ATTN_SCALE, 1.0, 1)
+    with pytest_raises(RuntimeError) as err:
+        out.grad_fn.apply(g)
+    assert 'msmc_attn_bwd failed with code -2' in str(err.value)
+
+
 def check_resblock_standalone(dev):
     """ResBlock1 called on its own (reference hifigan/common.py:44-51) against the stock operator chain: output, input
     gradient and every parameter gradient"""

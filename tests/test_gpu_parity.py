@@ -423,6 +423,18 @@ def test_attention_kernels_match_the_reference_chain():
     _parity.check_attention(DEV)
 
 
+def test_attention_kernels_beyond_one_tile_per_wave_stay_within_the_bf16_yardstick():
+    _parity.check_attention_tiles(DEV)
+
+
+def test_attention_kernels_padding_batch_and_repeat_invariance_bit_exact():
+    _parity.check_attention_exact_properties(DEV)
+
+
+def test_attention_wrapper_gradient_layouts_and_rejected_arguments():
+    _parity.check_attention_wrapper(DEV)
+
+
 def test_wave_exchange_primitives():
     """the shortlist search merges its per-lane candidates over lane groups with the gfx950 row / half swaps
     (v_permlane16_swap / v_permlane32_swap behind wave_xor16 / wave_xor32): a search whose winner, runner-up and third

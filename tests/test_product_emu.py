@@ -640,6 +640,18 @@ def test_attention_kernels_match_the_reference_chain():
     _parity.check_attention('cpu')
 
 
+def test_attention_kernels_beyond_one_tile_per_wave_stay_within_the_bf16_yardstick():
+    _parity.check_attention_tiles('cpu')
+
+
+def test_attention_kernels_padding_batch_and_repeat_invariance_bit_exact():
+    _parity.check_attention_exact_properties('cpu')
+
+
+def test_attention_wrapper_gradient_layouts_and_rejected_arguments():
+    _parity.check_attention_wrapper('cpu')
+
+
 @pytest.mark.parametrize('H,K,D,N', [
     (4, 64, 256, 100),     # all heads' images resident in LDS; ragged last tile
     (4, 256, 256, 70),     # one head at a time: one image buffer + one fp32 rows buffer in LDS, refilled in turns (d = 64)
