@@ -593,6 +593,65 @@ int msmc_bn_bwd(const void* g, const void* x, const float* mean, const float* rs
 int msmc_bn_eval_bwd(const void* g, const float* rstd, void* gx, long N, int C, int g_dtype, int dtype, msmc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The speaker reference encoder's own operators (csrc/tdnn.hip): ECAPA-TDNN, reference msmctts/networks/vqgantts/tdnn.py:67-244.
+ * Channels-last activations (``dtype``: 0 fp32, 1 bf16), statistics / sums / parameters and their gradients fp32; activation
+ * pointers, per-channel vectors and workspaces 16-byte aligned; every sum in a fixed order (no atomics): two calls on the same
+ * input are bit-identical.  MSMC_E_SHAPE for anything outside the stated constraints.
+ * ------------------------------------------------------------------------------------------- */
+/* ReLU + affine BatchNorm, bn(F.relu(conv(x))) with nn.BatchNorm1d defaults (tdnn.py:96-98, 115-116):
+ *   y = gamma * (relu(x) - mean) * rstd + beta  over rows x [N][C] at a row stride of ``ldx`` elements (ld >= C, ld % 8 == 0: a
+ *   channel slice of a wider row, as the Res2 branches normalise), y at ``ldy``.  C % 8 == 0, C <= 1024, N < 2^31.
+ * Bytes of scratch of the two-launch passes (0 for a refused shape). */
+size_t msmc_relu_bn_workspace(long N, int C);
+/* Training forward, two launches: per-slab Welford (count, mean, M2) of relu(x), then Chan's merge and the normalisation.  mean /
+ * rstd [C] are kept for the backward pass; running_mean / running_var (both or neither; unbiased variance) and
+ * num_batches_tracked (int64, may be NULL) advance on the device.  N < 2: MSMC_E_SHAPE. */
+int msmc_relu_bn_fwd(const void* x, long ldx, const float* gamma, const float* beta, void* y, long ldy, float* mean, float* rstd,
+                     float* running_mean, float* running_var, long long* num_batches_tracked, void* workspace,
+                     size_t workspace_bytes, long N, int C, float eps, float momentum, int dtype, msmc_stream stream);
+/* Evaluation forward, one launch, from the running statistics; rstd [C] (may be NULL) receives 1 / sqrt(running_var + eps). */
+int msmc_relu_bn_eval_fwd(const void* x, long ldx, const float* gamma, const float* beta, const float* running_mean,
+                          const float* running_var, void* y, long ldy, float* rstd, long N, int C, float eps, int dtype,
+                          msmc_stream stream);
+/* Training backward, two launches; the ReLU mask is recomputed from x, xhat = (relu(x) - mean) * rstd:
+ *   dbeta = sum g, dgamma = sum g xhat, gx = [x > 0] gamma rstd (g - dbeta / N - xhat dgamma / N); g at ``ldg``, gx at ``ldgx``. */
+int msmc_relu_bn_bwd(const void* g, long ldg, const void* x, long ldx, const float* mean, const float* rstd, const float* gamma,
+                     void* gx, long ldgx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, long N, int C,
+                     int dtype, msmc_stream stream);
+/* Evaluation backward: gx = [x > 0] gamma rstd g in one launch; with dgamma / dbeta (both or neither, then with the workspace)
+ * the per-slab sums run first. */
+int msmc_relu_bn_eval_bwd(const void* g, long ldg, const void* x, long ldx, const float* running_mean, const float* rstd,
+                          const float* gamma, void* gx, long ldgx, float* dgamma, float* dbeta, void* workspace,
+                          size_t workspace_bytes, long N, int C, int dtype, msmc_stream stream);
+/* Squeeze-excitation with the block's residual (tdnn.py:122-134, 150-151), x / res / y [B][T][C]:
+ *   y = res + x * gate[b],  gate = sigmoid(W2 relu(W1 mean_t(x) + b1) + b2),  W1 [C/2][C], W2 [C][C/2] (nn.Linear layout).
+ * C % 8 == 0, C <= 1024, B < 65536.  Forward, three launches: per-slab time sums, one workgroup per batch element (merge + the
+ * two matrix-vector products), scale + residual.  gate / mean [B][C] and hidden [B][C/2] (fp32) are kept for the backward. */
+size_t msmc_se_workspace(int B, int T, int C);
+int msmc_se_fwd(const void* x, const void* res, const float* W1, const float* b1, const float* W2, const float* b2, void* y,
+                float* gate, float* mean, float* hidden, void* workspace, size_t workspace_bytes, int B, int T, int C, int dtype,
+                msmc_stream stream);
+/* Backward over the frames: dgate [B][C] = sum_t g x (per-slab sums, merged in order), and, once the two small layers have been
+ * back-propagated on [B][C] quantities, gx = g * gate + dmean with dmean [B][C] the gradient of the time mean divided by T.
+ * (The residual's gradient is g itself.) */
+int msmc_se_bwd_gate(const void* g, const void* x, float* dgate, void* workspace, size_t workspace_bytes, int B, int T, int C,
+                     int dtype, msmc_stream stream);
+int msmc_se_bwd_apply(const void* g, const float* gate, const float* dmean, void* gx, int B, int T, int C, int dtype,
+                      msmc_stream stream);
+/* Attentive statistics pooling (tdnn.py:163-170) of x [B][T][C] under logits a [B][T][C] (the output of linear2):
+ *   alpha = softmax_t(a) over all T frames, mean = sum_t alpha x, std = sqrt(max(sum_t alpha x^2 - mean^2, 1e-9)),
+ *   out [B][2C] fp32 = (mean | std).  C % 8 == 0, C <= 1536, T >= 1, B < 65536.
+ * Forward, two launches: an online softmax per (batch, channel) over splits of T -- x and a are read once -- then the partials
+ * (m, l, s1, s2) merged in order.  stats [B][4][C] fp32 = (max, sum of exponentials, mean, residual) is kept for the backward. */
+size_t msmc_asp_workspace(int B, int T, int C);
+int msmc_asp_fwd(const void* x, const void* a, float* out, float* stats, void* workspace, size_t workspace_bytes, int B, int T,
+                 int C, int dtype, msmc_stream stream);
+/* Backward, one pass: alpha recomputed from stats; gx and ga [B][T][C] from gout [B][2C] fp32.  Where the clamp is active
+ * (residual < 1e-9) no gradient flows through std, as with torch.clamp. */
+int msmc_asp_bwd(const float* gout, const void* x, const void* a, const float* stats, void* gx, void* ga, int B, int T, int C,
+                 int dtype, msmc_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * O1  gradient-norm clipping + AdamW for all tensors of one child in three launches (csrc/optim.hip).
  * Replaces clip_grad_norm_ + the per-child AdamW step of
  *   reference msmctts/trainers/optimizers/__init__.py:53-78, msmctts/trainers/msmctts_trainer.py:205-206.

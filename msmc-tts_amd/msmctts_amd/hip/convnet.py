@@ -516,8 +516,9 @@ class ConvBank(object):
     @staticmethod
     def _grad_pairs(l):
         m = l.module
-        return (((m.bias, l.gb_view), (m.weight, l.gv_view)) if l.plain else
-                ((m.bias, l.gb_view), (m.weight_g, l.gg_view), (m.weight_v, l.gv_view)))
+        pairs = (((m.bias, l.gb_view), (m.weight, l.gv_view)) if l.plain else
+                 ((m.bias, l.gb_view), (m.weight_g, l.gg_view), (m.weight_v, l.gv_view)))
+        return pairs if m.bias is not None else pairs[1:]         # (bias=False layers: the speaker encoder's convolutions)
 
     _NO_ATOMICS = frozenset((3, 4, 5, 6, 7, 9))       # msmc_conv_wgrad variants that accumulate through a second stage into copy 0
 

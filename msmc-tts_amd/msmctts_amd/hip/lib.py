@@ -175,6 +175,21 @@ _SIGNATURES.update({
     'msmc_bn_eval_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _f, _i, _i, _vp]),
     'msmc_bn_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_long, _i, _i, _i, _vp]),
     'msmc_bn_eval_bwd': (_i, [_vp, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp]),
+    'msmc_relu_bn_workspace': (_sz, [ctypes.c_long, _i]),
+    'msmc_relu_bn_fwd': (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_long, _i,
+                         _f, _f, _i, _vp]),
+    'msmc_relu_bn_eval_fwd': (_i, [_vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _i, _f, _i, _vp]),
+    'msmc_relu_bn_bwd': (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _sz,
+                         ctypes.c_long, _i, _i, _vp]),
+    'msmc_relu_bn_eval_bwd': (_i, [_vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _sz,
+                              ctypes.c_long, _i, _i, _vp]),
+    'msmc_se_workspace': (_sz, [_i, _i, _i]),
+    'msmc_se_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    'msmc_se_bwd_gate': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    'msmc_se_bwd_apply': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'msmc_asp_workspace': (_sz, [_i, _i, _i]),
+    'msmc_asp_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    'msmc_asp_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'msmc_opt_chunk': (_i, []),
     'msmc_opt_clip_adamw': (_i, [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp]),
     'msmc_lrelu_bwd': (_i, [_vp, _vp, _vp, ctypes.c_long, _f, _i, _vp]),

@@ -9,8 +9,11 @@ quantiser (gfx950 VQ kernels, 1x1 stacks and prior predictor on the implicit-GEM
 HifiGAN generator are the ones of ``msmc_vqgan.py``.  New here: ``MAMSEncoder`` (the multi-stage encoder with an optional
 pitch / energy side encoder added to every stage's output) and the optional reference-encoder slot.
 
-The speaker / style reference encoder (``global_encoder_config._name == 'ECAPA_TDNN'``, reference tdnn.py) is not built: the
-shipped configuration does not use it; asking for it raises.
+The speaker / style reference encoder (``global_encoder_config._name == 'ECAPA_TDNN'``, reference :143-151) is ``tdnn.py``'s
+``ECAPA_TDNN(in_channels=mel_dim, embd_dim=n_model_size, channels=n_model_size)`` on the gfx950 kernels: its utterance-level
+embedding of ``ref`` (training: of ``mel`` when no ``ref`` is given) is added to every frame of the frame decoder's input
+(:195-199, :254-258).  Sizes its kernels do not take (``n_model_size % 64``, ``mel_dim % 8``) are refused at construction with
+``NotImplementedError``; an unknown encoder name raises ``ValueError`` as in the reference.
 """
 import torch
 import torch.nn as nn
@@ -20,6 +23,7 @@ from ...hip import norm as hipnorm
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
 from .msmc_vqgan import MultiStageQuantizer, PriorPredictor, _fft_pos
+from .tdnn import ECAPA_TDNN
 
 
 class AttrPredictor(PriorPredictor):
@@ -77,9 +81,11 @@ class MSMCVQGANEmb(nn.Module):
         self.in_linear = nn.Linear(emb_dim, n_model_size)
         self.encoder = MAMSEncoder(n_model_size, pitch_dim=pitch_dim, energy_dim=energy_dim, **encoder_config)
         if global_encoder_config is not None:
-            raise NotImplementedError('MSMCVQGANEmb: the reference encoder (global_encoder_config, ECAPA_TDNN of the '
-                                      "reference's tdnn.py) is outside this build; the shipped QS-TTS configuration "
-                                      'does not use it')
+            name = (global_encoder_config.get('_name') if isinstance(global_encoder_config, dict)
+                    else getattr(global_encoder_config, '_name', None))
+            if name != 'ECAPA_TDNN':
+                raise ValueError('Wrong global encoder: {}'.format(name))
+            self.global_encoder = ECAPA_TDNN(in_channels=mel_dim, embd_dim=n_model_size, channels=n_model_size)
         self.quantizer = MultiStageQuantizer(n_model_size, list(encoder_config['downsample_scales'])[::-1],
                                              **quantizer_config)
         decoder_config = dict(decoder_config)
@@ -90,7 +96,9 @@ class MSMCVQGANEmb(nn.Module):
         if pred_mel:
             self.mel_predictor = nn.Linear(n_model_size, mel_dim if mel_dim is not None else emb_dim)
 
-    def _decode_frames(self, x, lengths):
+    def _decode_frames(self, x, lengths, ref=None):
+        if hasattr(self, 'global_encoder'):
+            x = x + self.global_encoder(ref).unsqueeze(1).to(x.dtype)
         if hasattr(self, 'frame_decoder'):
             x, _ = self.frame_decoder(x, _fft_pos(lengths, x), lengths=lengths)
         return x
@@ -106,7 +114,7 @@ class MSMCVQGANEmb(nn.Module):
         out = {'encoder_outputs': feats[::-1], 'encoder_lengths': lens[::-1], 'content_representations': content,
                'encoder_indices': qs['quantizer_indices'], 'encoder_diffs': qs['quantizer_diffs'],
                'decoder_diffs': qs['predictor_diffs']}
-        dec_in = self._decode_frames(qs['residual_output'], emb_length)
+        dec_in = self._decode_frames(qs['residual_output'], emb_length, mel if ref is None else ref)
         if hasattr(self, 'mel_predictor'):
             out['mel_outputs'] = self.mel_predictor(dec_in)
         if window is not None:
@@ -131,7 +139,9 @@ class MSMCVQGANEmb(nn.Module):
         qs = quantizer_outputs
         if not isinstance(quantizer_outputs, dict):
             qs = self.quantizer(zip(quantizer_outputs, quantizer_lengths), from_encoder=False)
-        dec_in = self._decode_frames(qs['residual_output'], quantizer_lengths[-1])
+        if hasattr(self, 'global_encoder'):
+            assert ref is not None
+        dec_in = self._decode_frames(qs['residual_output'], quantizer_lengths[-1], ref)
         wav = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
         if self.training:
             out = {'decoder_outputs': wav}
