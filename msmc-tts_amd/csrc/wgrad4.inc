@@ -1,4 +1,4 @@
-// wgrad4.inc -- fourth-generation bf16 weight gradient (included by conv.hip after the second / third generation).
+// wgrad4.inc -- fourth-generation bf16 weight gradient (included by conv_wgrad.hip after the second / third generation).
 //
 // Same result contract as the third generation (split partial results in a workspace, summed in split order by
 // conv_wgrad_reduce_kernel; one split accumulates straight into dW), different operand movement.  Generations 2 / 3

@@ -1,4 +1,4 @@
-// wgrad5.inc -- bf16 weight gradient on the GENERAL lattice with LDS-DMA staging (included by conv.hip after wgrad4.inc).
+// wgrad5.inc -- bf16 weight gradient on the GENERAL lattice with LDS-DMA staging (included by conv_wgrad.hip after wgrad4.inc).
 //
 // Descriptor variant 7 only, not a tuner candidate yet: checked on the kernel interpreter (tests/test_product_emu.py) and
 // timed once on the GPU (profiles/r02_wgrad5_first_measurement.txt: correct, 15 % ahead of generation 3 on the stride-3

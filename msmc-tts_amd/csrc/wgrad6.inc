@@ -1,4 +1,4 @@
-// wgrad6.inc -- direct (vector ALU) bf16 weight gradient for THIN layers (desc.variant = 8; included by conv.hip).
+// wgrad6.inc -- direct (vector ALU) bf16 weight gradient for THIN layers (desc.variant = 8; included by conv_wgrad.hip).
 //
 // The first layers of the resolution / period discriminators (reference msmctts/networks/hifigan/discriminator.py:15-154: DiscriminatorR /
 // DiscriminatorP; spectrogram or waveform in, 1-16 channels) and their 1-channel output convolutions have weight

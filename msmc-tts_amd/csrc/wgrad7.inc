@@ -1,4 +1,4 @@
-// wgrad7.inc -- bf16 weight gradient on 128 x 128 channel tiles (descriptor variant 9; included by conv.hip after wgrad6.inc).
+// wgrad7.inc -- bf16 weight gradient on 128 x 128 channel tiles (descriptor variant 9; included by conv_wgrad.hip after wgrad6.inc).
 //
 // Reference layers: the k = 3 feed-forward convolutions of the predictor's FFT blocks at B = 64 (600 <-> 1536 channels over
 // 25 600 frames: msmctts/networks/acoustic_models/transformer.py:330-352, examples/csmsc/configs/msmc_vq_gan_am.yaml) -- any
@@ -288,10 +288,8 @@ static int wg7_launch(const msmc_conv_desc* d, const void* g, float* dw, float* 
     Wg4Plan pl;
     int rc = wg7_plan(d, g, &pl);
     if (rc) return rc;
-    if (pl.ws_floats) {
-        if (!ws || ws_floats < pl.ws_floats) return MSMC_E_WORKSPACE;
-        pl.P.ws = ws;
-    }
+    rc = wg3_take_ws(pl.ws_floats, ws, ws_floats, &pl.P.ws);
+    if (rc) return rc;
     const dim3 grid(pl.gx, pl.gy, pl.gz);
     const unsigned short* gp = (const unsigned short*)g;
 #define WG7_GO(TP)                                                                                           \
@@ -308,17 +306,5 @@ static int wg7_launch(const msmc_conv_desc* d, const void* g, float* dw, float* 
     msmc_conv_last = msmc_prof_name(msmc_kname("conv_wgrad7_kernel", nullptr, pl.tpw, -1));
     rc = msmc_check_launch();
     if (rc || !pl.P.ws) return rc;
-    const long n_dw = (long)d->ntaps * d->Cout * d->Cin;
-    float* mid = ws + (size_t)pl.gx * pl.P.ws_stride;
-    for (int level = 0; level < 2; ++level) {
-        WgReduceArgs a;
-        a.n = 0;
-        int blocks = 0;
-        wg3_reduce_add(a, &blocks, ws, pl.P.ws_stride, n_dw, db ? d->Cout : 0, (int)pl.gx, mid, dw, db, level);
-        if (!a.n) continue;
-        a.first[a.n] = blocks;
-        rc = wg3_reduce_launch(a, blocks, stream);
-        if (rc) return rc;
-    }
-    return 0;
+    return wg3_reduce_single(d, ws, pl.P.ws_stride, (int)pl.gx, dw, db, stream);
 }

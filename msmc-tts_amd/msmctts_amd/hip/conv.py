@@ -1,4 +1,5 @@
-"""Channels-last implicit-GEMM convolution ops over csrc/conv.hip (C ABI: msmc_conv_* in include/msmc_hip.h).
+"""Channels-last implicit-GEMM convolution ops over csrc/conv.hip (forward, data gradient), csrc/conv_wgrad.hip (weight
+gradient) and csrc/wnorm.hip (column sums, reflect-fold, leaky-ReLU backward); C ABI: msmc_conv_* in include/msmc_hip.h.
 
 Geometry helpers turn a PyTorch-style convolution (kernel, stride, dilation, padding, zero/reflect) into the
 lattice + tap-table descriptors the gather kernel consumes, for

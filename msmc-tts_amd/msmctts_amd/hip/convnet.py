@@ -418,7 +418,7 @@ class ConvBank(object):
             it.A, it.Bc, it.T = A, v.shape[1], l.taps
             it.dtype = 0 if dtype == torch.float32 else 1
             it.block0 = blk
-            it.tblock0 = tblk                      # tiles (rows x columns x all taps) of the layout pass, csrc/conv.hip wn_layout_kernel
+            it.tblock0 = tblk                      # tiles (rows x columns x all taps) of the layout pass, csrc/wnorm.hip wn_layout_kernel
             tblk += int(lib.get().msmc_wn_tile_blocks(A, v.shape[1], l.taps))
             it.nbias = l.cout
             it.db, it.gb = self.db.data_ptr() + odb * 4, self.gb.data_ptr() + ob * 4

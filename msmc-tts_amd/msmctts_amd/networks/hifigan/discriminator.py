@@ -17,7 +17,7 @@ from ...utils.audio import TorchSTFT
 from ..layers import WNConv2d
 from .common import get_padding
 
-# Arithmetic: channels-last on the gfx950 implicit-GEMM kernels (csrc/conv.hip).  MPD fuses each
+# Arithmetic: channels-last on the gfx950 implicit-GEMM kernels (csrc/conv.hip, csrc/conv_wgrad.hip).  MPD fuses each
 # leaky-ReLU into the consuming convolution's load (its feature maps are the raw outputs); MRD fuses it
 # into the producing convolution's epilogue (its feature maps are the activated outputs) and the
 # ReflectionPad2d into the load; feature maps are handed to the trainer as NCHW-shaped views.

@@ -1,7 +1,7 @@
 """HifiGAN generator (drop-in for reference msmctts/networks/hifigan/generator.py:10-64).
 
 Same constructor, parameter names and numerics; the arithmetic runs channels-last on the gfx950
-implicit-GEMM kernels (csrc/conv.hip): every leaky-ReLU is fused into the consuming convolution's
+implicit-GEMM kernels (csrc/conv.hip, csrc/conv_wgrad.hip): every leaky-ReLU is fused into the consuming convolution's
 load, the residual add, the sum over the three parallel ResBlocks and the ``/ num_kernels`` into
 the producing convolution's epilogue, the transposed convolutions are phase-decomposed gathers and
 weight norm is folded into one weight-preparation launch per forward.

@@ -335,3 +335,109 @@ def check_mixed_family_groups(device, report=None):
     assert fwd[1] == MIXED_FORWARD_KERNELS, fwd
     assert wg[0] == MIXED_WGRAD_LAUNCHES, wg
     assert wg[1] == MIXED_WGRAD_KERNELS, wg
+
+
+# ---- process state shared by the forward (csrc/conv.hip) and the weight-gradient (csrc/conv_wgrad.hip) unit ------------
+# What check_conv_shared_state observes, per dtype: launch-count deltas and msmc_conv_last_kernel() names.  Recorded by
+# running this same check against the kernel interpreter built from the commit BEFORE conv.hip was split into three
+# translation units (one unit, every switch a single static); the split must leave them as they are.
+SHARED_STATE = {
+    'bf16': {'forward': [1, 'conv_gather2_kernel<unsigned short, 1, 2, 4>'],
+             'wgrad': [1, 'conv_wgrad2_kernel<3>'],
+             'forward_group, grouping 1': 1, 'forward_group, grouping 0': 2,
+             'wgrad_group, grouping 1': 1, 'wgrad_group, grouping 0': 2,
+             # (64 bf16 channels are two channel chunks: too shallow for the pipelined forward, and the second-generation
+             #  bf16 weight gradient does not read the switch)
+             'forward gen 1': [1, 'conv_gather_kernel<unsigned short, 1>'],
+             'forward gen 1, pipeline 0': [1, 'conv_gather_kernel<unsigned short, 1>'],
+             'wgrad, pipeline 0': [1, 'conv_wgrad2_kernel<3>']},
+    'fp32': {'forward': [1, 'conv_gather2_kernel<float, 1, 2, 4>'],
+             'wgrad': [1, 'conv_wgrad_kernel<float, 4, 1>'],
+             'forward_group, grouping 1': 1, 'forward_group, grouping 0': 2,
+             'wgrad_group, grouping 1': 2, 'wgrad_group, grouping 0': 2,    # (no fp32 group kernel: one launch per member)
+             'forward gen 1': [1, 'conv_gather_pipe_kernel<float, 1, 1>'],
+             'forward gen 1, pipeline 0': [1, 'conv_gather_kernel<float, 1>'],
+             'wgrad, pipeline 0': [1, 'conv_wgrad_kernel<float, 4, 0>']},
+}
+SHARED_FRESH_THREAD = (0, '')           # launch count and last-kernel name a thread sees before its first call
+
+
+def check_conv_shared_state(device, report=None):
+    """The launch counter, the last-kernel slot and the grouping / pipeline switches are ONE object each for the forward and
+    the weight-gradient kernels: both directions move the same counter and name slot, msmc_conv_set_grouping(0) and
+    msmc_conv_set_pipeline(0) reach both, and counter and slot stay per thread.  Layer: B = 1, 1 x 40 lattice, 64 -> 64
+    channels, 1 x 3 kernel, alone and as a group of two.  ``report``: called with the observed figures before they are
+    compared (recording)."""
+    import ctypes
+    import threading
+    from msmctts_amd.hip import conv, lib
+    L = lib.get()
+    torch.manual_seed(0)
+    count, last = L.msmc_conv_launch_count, lambda: L.msmc_conv_last_kernel().decode()
+    geom = conv.Geometry(1, 40, (1, 3), (1, 1), (1, 1), (0, 1), False)
+    vp = ctypes.c_void_p * 2
+
+    def observe(dtype):
+        x = torch.randn(1, 1, 40, 64, device=device).to(dtype)
+        w = (torch.randn(3, 64, 64, device=device) / 14).to(dtype)
+        g = torch.randn(1, 1, 40, 64, device=device).to(dtype)
+        st = lib.stream(x)
+        fd, out = conv._forward_desc(x=x, w=w, geom=geom, in_slope=0.1)
+        wd = conv._build_desc(x.dtype, 1, 1, 40, 64, 1, 40, 64, geom.fwd_lattice, geom.fwd_taps, 0, 0.1, 1.0, 1.0, 1.0)
+        wd.x = wd.w = wd.out = x.data_ptr()
+        wd.dw_copies = 1
+        need = L.msmc_conv_wgrad_workspace(ctypes.byref(wd), g.data_ptr())
+        ws = torch.zeros(max(1, 2 * need // 4), device=device)
+        dw, db = torch.zeros(2, 3, 64, 64, device=device), torch.zeros(2, 64, device=device)
+        farr, warr = (lib.ConvDesc * 2)(fd, fd), (lib.ConvDesc * 2)(wd, wd)
+
+        def forward():
+            lib.check(L.msmc_conv_gather(ctypes.byref(fd), st), 'msmc_conv_gather')
+
+        def wgrad():
+            lib.check(L.msmc_conv_wgrad_ws(ctypes.byref(wd), g.data_ptr(), dw[0].data_ptr(), db[0].data_ptr(),
+                                           ws.data_ptr(), need, st), 'msmc_conv_wgrad_ws')
+
+        def forward_group():
+            lib.check(L.msmc_conv_gather_group(farr, 2, st), 'msmc_conv_gather_group')
+
+        def wgrad_group():
+            lib.check(L.msmc_conv_wgrad_group_ws(warr, vp(g.data_ptr(), g.data_ptr()), vp(dw[0].data_ptr(), dw[1].data_ptr()),
+                                                 vp(db[0].data_ptr(), db[1].data_ptr()), 2, ws.data_ptr(), 2 * need, st),
+                      'msmc_conv_wgrad_group_ws')
+
+        def run(fn):                    # [launch-count delta, last-kernel name] of one call
+            n0 = count()
+            fn()
+            return [count() - n0, last()]
+
+        seen = {'forward': run(forward), 'wgrad': run(wgrad)}
+        for on in (1, 0):
+            L.msmc_conv_set_grouping(on)
+            try:
+                seen['forward_group, grouping %d' % on] = run(forward_group)[0]
+                seen['wgrad_group, grouping %d' % on] = run(wgrad_group)[0]
+            finally:
+                L.msmc_conv_set_grouping(1)
+        fd.variant = 1                  # first-generation forward kernels: the ones the pipeline switch chooses between
+        seen['forward gen 1'] = run(forward)
+        L.msmc_conv_set_pipeline(0)
+        try:
+            seen['forward gen 1, pipeline 0'] = run(forward)
+            seen['wgrad, pipeline 0'] = run(wgrad)
+        finally:
+            L.msmc_conv_set_pipeline(1)
+        if torch.device(device).type == 'cuda':
+            torch.cuda.synchronize()
+        return seen
+
+    seen = {'bf16': observe(torch.bfloat16), 'fp32': observe(torch.float32)}
+    fresh = []
+    t = threading.Thread(target=lambda: fresh.append((count(), last())))
+    t.start()
+    t.join()
+    if report:
+        report(seen, fresh[0])
+    assert count() > 0 and last() != ''                     # (so the fresh thread's figures are its own)
+    assert seen == SHARED_STATE, seen
+    assert fresh[0] == SHARED_FRESH_THREAD, fresh

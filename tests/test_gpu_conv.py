@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the implicit-GEMM convolution kernels (csrc/conv.hip) at the CSMSC layer shapes against
+"""GPU (-m gpu): the implicit-GEMM convolution kernels (csrc/conv.hip, csrc/conv_wgrad.hip) at the CSMSC layer shapes against
 PyTorch-ROCm's own convolutions on the same device (fp32 reference of the same op), forward, data gradient
 and weight gradient; fp32 kernels within 2e-4 of the output scale, bf16 kernels within 2e-2."""
 import pytest
@@ -9,7 +9,8 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
 
-from _convcases import CONVS, SMALL, check_conv_case, check_mixed_family_groups, cl, conv_part_errors, nchw, rel
+from _convcases import (CONVS, SMALL, check_conv_case, check_conv_shared_state, check_mixed_family_groups, cl, conv_part_errors,
+                        nchw, rel)
 
 
 @pytest.mark.parametrize('dtype,tol', [(torch.float32, 2e-4), (torch.bfloat16, 2e-2)])
@@ -29,6 +30,11 @@ def test_grouped_calls_with_members_of_several_kernel_families():
     """the members of tests/test_product_emu.py's test of the same name on the device: bit-equal to single launches, the same
     launch count and launch log"""
     check_mixed_family_groups(DEV)
+
+
+def test_conv_state_shared_by_forward_and_weight_gradient():
+    """tests/test_product_emu.py's test of the same name on the device: the same launch counts and kernel names"""
+    check_conv_shared_state(DEV)
 
 
 @pytest.mark.parametrize('gen', [1, 2, 3])

@@ -515,6 +515,12 @@ def test_grouped_calls_with_members_of_several_kernel_families():
     _convcases.check_mixed_family_groups('cpu')
 
 
+def test_conv_state_shared_by_forward_and_weight_gradient():
+    """launch counter, last-kernel slot, grouping and pipeline switch: one object each for csrc/conv.hip and
+    csrc/conv_wgrad.hip, counter and slot per thread (_convcases.check_conv_shared_state)"""
+    _convcases.check_conv_shared_state('cpu')
+
+
 def test_wgrad_fourth_generation_grouped():
     """msmc_conv_wgrad_group_ws4(group4 = 1): the fourth-generation members of a grouped call share one grid of their own
     kernel (members of different tap counts: the widest sets the accumulator budget), a member outside the scope goes the
