@@ -188,7 +188,7 @@ typedef struct msmc_conv_desc {
 } msmc_conv_desc;
 
 /* ---------------------------------------------------------------------------------------------
- * Attention core of the FFT blocks (bf16, head size 64): softmax(q k^T * scale + bias) (dropout) v per (batch, head),
+ * Attention core of the FFT blocks (bf16; fp32: the _f32 pair below; head size 64): softmax(q k^T * scale + bias) (dropout) v per (batch, head),
  * q / k / v read in place from the fused projection, heads merged on the way out.  Replaces
  *   ScaledDotProductAttention.forward + head split / merge   reference acoustic_models/transformer.py:237-259,296-315
  * qkv [B][T][H][192] bf16 (q | k | v, 64 each); bias [B][Tp] fp32 additive key bias (0 = attend, -inf = padding), Tp = T
@@ -204,6 +204,15 @@ int msmc_attn_fwd(const void* qkv, const float* bias, void* out, float* lse, int
 int msmc_attn_bwd(const void* qkv, const float* bias, const void* out, const float* lse, const void* dout, void* dqkv,
                   float* dsum, int B, int T, int H, int Tp, float scale, float p_drop, const long long* seed, long long salt,
                   msmc_stream stream);
+/* The same two calls with fp32 storage (qkv, out, dout, dqkv fp32 in the same layouts; bias, lse, dsum as above): the
+ * products run on the exact-fp32 matrix instruction and the exponentials are the accurate ones, so the fp32 parity bar
+ * applies.  For the same (seed word, salt, B, T, H, p_drop) they drop exactly the entries the bf16 calls drop.  Return
+ * codes as above: MSMC_E_SHAPE for Tp % 32 != 0, Tp < T or p_drop >= 1 (nothing is launched). */
+int msmc_attn_fwd_f32(const float* qkv, const float* bias, float* out, float* lse, int B, int T, int H, int Tp, float scale,
+                      float p_drop, const long long* seed, long long salt, msmc_stream stream);
+int msmc_attn_bwd_f32(const float* qkv, const float* bias, const float* out, const float* lse, const float* dout, float* dqkv,
+                      float* dsum, int B, int T, int H, int Tp, float scale, float p_drop, const long long* seed,
+                      long long salt, msmc_stream stream);
 
 /* out[q] = epilogue( sum_t sum_ci w[tap_w[t]][co][ci] * act(x[in(q, t)][ci]) + bias[co] ). */
 int msmc_conv_gather(const msmc_conv_desc* desc, msmc_stream stream);

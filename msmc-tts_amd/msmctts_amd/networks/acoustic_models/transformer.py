@@ -6,9 +6,9 @@ with -inf, conv feed-forward, output zeroed on padding after both sub-layers.  O
 forward: the fused-QKV and output projections are 1-tap convolutions on the gfx950 implicit-GEMM
 kernels (bias fused, activations stay in the compute dtype: no cast kernels), the position-wise convolutions run on
 the same kernels, and ``layer_norm(dropout(h) + residual) * non_pad_mask`` is one fused kernel per sub-layer
-(csrc/norm.hip, masks regenerated in the backward pass).  The softmax-attention core runs on csrc/attn.hip (bf16, head size 64:
-the benchmarked configuration); fp32 runs -- the parity configuration -- and other head sizes use PyTorch-ROCm's fused
-``scaled_dot_product_attention`` on strided views of the QKV projection.  There is no stock-operator version of the block
+(csrc/norm.hip, masks regenerated in the backward pass).  The softmax-attention core runs on csrc/attn.hip (head size 64; bf16:
+the benchmarked configuration, fp32: the parity configuration, on the exact-fp32 kernels); other head sizes -- and fp32 with
+MSMC_ATTN_FP32=0, an A/B switch -- use PyTorch-ROCm's fused ``scaled_dot_product_attention`` on strided views of the QKV projection.  There is no stock-operator version of the block
 stack: on a device without the library (or the test interpreter) the forward raises.
 """
 import os
@@ -211,8 +211,8 @@ class FFTBlocks(nn.Module):
         # boolean mask is converted to this by every attention call: a where + fills per layer)
         att0 = self.layer_stack[0].slf_attn
         if hipattn.supported(self.hip_dtype, att0.d_k, att0.d_v):
-            key_keep = (hipattn.pad_key_bias(pos),)      # csrc/attn.hip (bf16, head size 64)
-        else:                                            # the stock fused operator (fp32 parity runs, other head sizes)
+            key_keep = (hipattn.pad_key_bias(pos),)      # csrc/attn.hip (bf16 or fp32, head size 64)
+        else:                                            # the stock fused operator (other head sizes, MSMC_ATTN_FP32=0)
             key_keep = torch.zeros(pos.shape[0], 1, 1, pos.shape[1], dtype=self.hip_dtype, device=pos.device).masked_fill_(
                 pos.eq(0).view(pos.shape[0], 1, 1, pos.shape[1]), float('-inf'))
         out = out.to(self.hip_dtype)
