@@ -401,6 +401,12 @@ int msmc_mrd_image_bwd_dt(const float* mel, const void* gimg, float* gmel, int B
                           msmc_stream stream);
 int msmc_mrd_image_bwd(const float* mel, const float* gimg, float* gmel, int B, int T, int F, int FP,
                        msmc_stream stream);
+/* One channel of that image alone, channels-last [B][F][T][1] ('linear' domain: channel = 0, the magnitude; 'log' domain:
+ * channel = 1, the normalised log-magnitude): the forward value is that channel of msmc_mrd_image_fwd_dt bit for bit, the other
+ * channel is neither computed nor stored; the gradient of channel 1 is zero where the clamp is active. */
+int msmc_mrd_image1_fwd_dt(const float* mel, void* img, int B, int T, int F, int FP, int channel, int dtype, msmc_stream stream);
+int msmc_mrd_image1_bwd_dt(const float* mel, const void* gimg, float* gmel, int B, int T, int F, int FP, int channel, int dtype,
+                           msmc_stream stream);
 
 /* Waveform fan-out of the discriminator (reference msmctts/networks/hifigan/discriminator.py:102-116,135-145,180-190): the period
  * sub-discriminators read the waveform cast to the stack's dtype and reflection-padded on the right to a multiple of their
@@ -416,7 +422,8 @@ int msmc_wave_fan_bwd(const float* const* g32, int n32, const void* const* gcopi
  * step: five framings, five magnitudes, five images -- forward and backward).  kind: 0 msmc_stft_frames_fwd (a = x, out = frames),
  * 1 _bwd (a = gframes, out = gx), 2 msmc_spec_mag_fwd (a = spec, out = mag), 3 _bwd (a = spec, b = mag, c = gmag, out = gspec),
  * 4 msmc_mrd_image_fwd_dt (a = mel, out = img), 5 _bwd_dt (a = mel, b = gimg, out = gmel), 6 msmc_log_clamp_fwd (a = x, out = y, R = n),
- * 7 _bwd (a = x, b = g, out = gx, R = n); the remaining fields are the arguments of those entry points. */
+ * 7 _bwd (a = x, b = g, out = gx, R = n), 8 msmc_mrd_image1_fwd_dt (a = mel, out = img, channel), 9 _bwd_dt (a = mel, b = gimg,
+ * out = gmel, channel); the remaining fields are the arguments of those entry points. */
 #define MSMC_SPECTRAL_MULTI_MAX 8
 typedef struct msmc_spectral_op {
     int kind, dtype;
@@ -428,6 +435,7 @@ typedef struct msmc_spectral_op {
     int F, CP, FP, clamp_mode;
     float lo;
     long R;
+    int channel;
 } msmc_spectral_op;
 int msmc_spectral_multi(const msmc_spectral_op* ops, int n, msmc_stream stream);
 /* Vocoder windows of a captured step (reference msmctts_trainer.py:211-219, window starts on the device): frames[b][i] = starts[b] + i

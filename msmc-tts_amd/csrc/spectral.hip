@@ -167,6 +167,125 @@ __global__ __launch_bounds__(256) void mrd_image_bwd_kernel(const float* __restr
     mrd_image_bwd_body<O>(mel, gimg, gmel, T, F, FP, total, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// Single-channel image [B][F][T][1] (the 'linear' / 'log' domains of the resolution discriminators, reference audio.py:410-415):
+// CH = 0 the magnitude, CH = 1 the normalised log-magnitude, each by the expression of the same channel of mrd_image_fwd_body --
+// the value is that channel bit for bit, and the other channel is neither computed nor stored.  With one channel a lane that owned
+// one (f, t) would store 2 (bf16) or 4 bytes; here a lane owns FOUR consecutive elements of the flat image (consecutive t, across a
+// row end where T is no multiple of 4) and stores them as one 8-byte (bf16) or 16-byte (fp32) vector.  An image whose base is not
+// aligned to the run, and the last partial run, are stored element by element.
+MSMC_DEV void sp_store4(float* p, const float (&v)[4]) { f32x4 o = {v[0], v[1], v[2], v[3]}; *(f32x4*)p = o; }
+MSMC_DEV void sp_store4(unsigned short* p, const float (&v)[4]) {
+    u32x2 o = {(unsigned int)f32_to_bf16_bits(v[0]) | ((unsigned int)f32_to_bf16_bits(v[1]) << 16),
+               (unsigned int)f32_to_bf16_bits(v[2]) | ((unsigned int)f32_to_bf16_bits(v[3]) << 16)};
+    *(u32x2*)p = o;
+}
+MSMC_DEV void sp_store1(float* p, float a) { *p = a; }
+MSMC_DEV void sp_store1(unsigned short* p, float a) { *p = f32_to_bf16_bits(a); }
+MSMC_DEV float sp_load1(const float* p) { return *p; }
+MSMC_DEV float sp_load1(const unsigned short* p) { return bf16_bits_to_f32(*p); }
+template <typename O, int CH>
+MSMC_DEV void mrd_image1_fwd_body(const float* __restrict__ mel, O* __restrict__ img, int T,
+                                                            int F, int FP, long total, int bid, int nb) {
+    const bool vec = ((size_t)img % (4 * sizeof(O))) == 0;
+    const long nrun = (total + 3) / 4;
+    for (long q = (long)bid * 256 + threadIdx.x; q < nrun; q += (long)nb * 256) {
+        const long e0 = q * 4;
+        int t = (int)(e0 % T);
+        long r = e0 / T;
+        int f = (int)(r % F);
+        long b = r / F;
+        float m4[4], v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {                   // (the four strided reads leave together)
+            m4[u] = e0 + u < total ? mel[(b * T + t) * FP + f] : 1.f;
+            if (++t == T) {
+                t = 0;
+                if (++f == F) { f = 0; ++b; }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float m = m4[u];
+            if (CH == 0) {
+                v[u] = m;
+            } else {
+                float lg = (20.f * log10f(m) - 20.f + 100.f) / 100.f;
+                lg = lg < 0.f ? 0.f : (lg > 1.f ? 1.f : lg);
+                v[u] = lg;
+            }
+        }
+        if (vec && e0 + 4 <= total) {
+            sp_store4(img + e0, v);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (e0 + u < total) sp_store1(img + e0 + u, v[u]);
+        }
+    }
+}
+template <typename O, int CH>
+__global__ __launch_bounds__(256) void mrd_image1_fwd_kernel(const float* __restrict__ mel, O* __restrict__ img, int T,
+                                                            int F, int FP, long total) {
+    mrd_image1_fwd_body<O, CH>(mel, img, T, F, FP, total, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// gmel[b][t][f] from the single-channel image gradient gimg[b][f][t]: CH = 0 the gradient itself, CH = 1 times d lg / d m inside
+// the clamp and zero where the clamp is active (as channel 1 of mrd_image_bwd_body); columns F..FP-1 zero.  A lane owns four
+// consecutive f of one (b, t): mel and gmel move as 16-byte vectors when FP is a multiple of 4 and both are 16-byte aligned.
+template <int CH>
+MSMC_DEV float sp_image1_grad(float m, float gi) {
+    if (CH == 0) return gi;
+    const float lg = (20.f * log10f(m) - 20.f + 100.f) / 100.f;
+    return (lg > 0.f && lg < 1.f) ? gi * (0.2f / (2.302585092994046f * m)) : 0.f;
+}
+template <typename O, int CH>
+MSMC_DEV void mrd_image1_bwd_body(const float* __restrict__ mel, const O* __restrict__ gimg,
+                                                            float* __restrict__ gmel, int T, int F, int FP, long total, int bid, int nb) {
+    const bool vec = (FP % 4) == 0 && ((size_t)mel % 16) == 0 && ((size_t)gmel % 16) == 0;
+    const long nrun = (total + 3) / 4;
+    for (long q = (long)bid * 256 + threadIdx.x; q < nrun; q += (long)nb * 256) {
+        const long e0 = q * 4;
+        if (vec) {                                      // (total = B T FP is a multiple of 4 and the run stays in one row)
+            const int f0 = (int)(e0 % FP);
+            const long r = e0 / FP;                     // b*T + t
+            const int t = (int)(r % T);
+            const long b = r / T;
+            const f32x4 m4 = *(const f32x4*)(mel + e0);
+            float gi[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) gi[u] = f0 + u < F ? sp_load1(gimg + ((b * F + f0 + u) * (long)T) + t) : 0.f;
+            f32x4 g4;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) g4[u] = f0 + u < F ? sp_image1_grad<CH>(m4[u], gi[u]) : 0.f;
+            *(f32x4*)(gmel + e0) = g4;
+            continue;
+        }
+        for (long e = e0; e < e0 + 4 && e < total; ++e) {
+            const int f = (int)(e % FP);
+            const long r = e / FP;
+            const int t = (int)(r % T);
+            const long b = r / T;
+            gmel[e] = f < F ? sp_image1_grad<CH>(mel[e], sp_load1(gimg + ((b * F + f) * (long)T) + t)) : 0.f;
+        }
+    }
+}
+template <typename O, int CH>
+__global__ __launch_bounds__(256) void mrd_image1_bwd_kernel(const float* __restrict__ mel, const O* __restrict__ gimg,
+                                                            float* __restrict__ gmel, int T, int F, int FP, long total) {
+    mrd_image1_bwd_body<O, CH>(mel, gimg, gmel, T, F, FP, total, (int)blockIdx.x, (int)gridDim.x);
+}
+// (dtype, channel) -> instantiation of a single-channel image body or kernel
+#define SP_IMAGE1(dtype, channel, GO)                             \
+    do {                                                          \
+        if ((dtype) == 0) {                                       \
+            if ((channel) == 0) GO(float, 0);                     \
+            else GO(float, 1);                                    \
+        } else {                                                  \
+            if ((channel) == 0) GO(unsigned short, 0);            \
+            else GO(unsigned short, 1);                           \
+        }                                                         \
+    } while (0)
+
 MSMC_DEV void log_clamp_fwd_body(const float* __restrict__ x, float* __restrict__ y, long n,
                                                            float lo, int bid, int nb) {
     for (long e = (long)bid * 256 + threadIdx.x; e < n; e += (long)nb * 256) {
@@ -214,6 +333,18 @@ __global__ __launch_bounds__(256) void spectral_multi_kernel(SpMultiArgs a) {
             if (o.dtype == 0) mrd_image_fwd_body<float>((const float*)o.a, (float*)o.out, o.T, o.F, o.FP, (long)o.B * o.F * o.T, bid, nb);
             else mrd_image_fwd_body<unsigned short>((const float*)o.a, (unsigned short*)o.out, o.T, o.F, o.FP, (long)o.B * o.F * o.T, bid, nb);
             break;
+        case 8: {
+#define SP_GO(O_, CH_) mrd_image1_fwd_body<O_, CH_>((const float*)o.a, (O_*)o.out, o.T, o.F, o.FP, (long)o.B * o.F * o.T, bid, nb)
+            SP_IMAGE1(o.dtype, o.channel, SP_GO);
+#undef SP_GO
+            break;
+        }
+        case 9: {
+#define SP_GO(O_, CH_) mrd_image1_bwd_body<O_, CH_>((const float*)o.a, (const O_*)o.b, (float*)o.out, o.T, o.F, o.FP, (long)o.B * o.T * o.FP, bid, nb)
+            SP_IMAGE1(o.dtype, o.channel, SP_GO);
+#undef SP_GO
+            break;
+        }
         case 6: log_clamp_fwd_body((const float*)o.a, (float*)o.out, o.R, o.lo, bid, nb); break;
         case 7: log_clamp_bwd_body((const float*)o.a, (const float*)o.b, (float*)o.out, o.R, o.lo, bid, nb); break;
         default:
@@ -358,6 +489,28 @@ int msmc_mrd_image_bwd_dt(const float* mel, const void* gimg, float* gmel, int B
                     (const unsigned short*)gimg, gmel, T, F, FP, total);
     return msmc_check_launch();
 }
+int msmc_mrd_image1_fwd_dt(const float* mel, void* img, int B, int T, int F, int FP, int channel, int dtype, msmc_stream stream) {
+    if (!mel || !img || B <= 0 || T <= 0 || F <= 0 || FP < F || channel < 0 || channel > 1 || dtype < 0 || dtype > 1) return MSMC_E_SHAPE;
+    const long total = (long)B * F * T;
+#define SP_GO(O_, CH_)                                                                                                          \
+    MSMC_LAUNCH((mrd_image1_fwd_kernel<O_, CH_>), sp_grid((total + 3) / 4), dim3(256), 0, (msmc_stream_t)stream, mel, (O_*)img, T, F, \
+                FP, total)
+    SP_IMAGE1(dtype, channel, SP_GO);
+#undef SP_GO
+    return msmc_check_launch();
+}
+int msmc_mrd_image1_bwd_dt(const float* mel, const void* gimg, float* gmel, int B, int T, int F, int FP, int channel, int dtype,
+                           msmc_stream stream) {
+    if (!mel || !gimg || !gmel || B <= 0 || T <= 0 || F <= 0 || FP < F || channel < 0 || channel > 1 || dtype < 0 || dtype > 1)
+        return MSMC_E_SHAPE;
+    const long total = (long)B * T * FP;
+#define SP_GO(O_, CH_)                                                                                                          \
+    MSMC_LAUNCH((mrd_image1_bwd_kernel<O_, CH_>), sp_grid((total + 3) / 4), dim3(256), 0, (msmc_stream_t)stream, mel,            \
+                (const O_*)gimg, gmel, T, F, FP, total)
+    SP_IMAGE1(dtype, channel, SP_GO);
+#undef SP_GO
+    return msmc_check_launch();
+}
 int msmc_mrd_image_fwd(const float* mel, float* img, int B, int T, int F, int FP, msmc_stream stream) {
     return msmc_mrd_image_fwd_dt(mel, img, B, T, F, FP, 0, stream);
 }
@@ -442,6 +595,11 @@ int msmc_spectral_multi(const msmc_spectral_op* ops, int n, msmc_stream stream) 
             case 4: case 5:
                 if (o.B <= 0 || o.T <= 0 || o.F <= 0 || o.FP < o.F || o.dtype < 0 || o.dtype > 1 || (o.kind == 5 && !o.b)) return MSMC_E_SHAPE;
                 total = o.kind == 4 ? (long)o.B * o.F * o.T : (long)o.B * o.T * o.FP;
+                break;
+            case 8: case 9:
+                if (o.B <= 0 || o.T <= 0 || o.F <= 0 || o.FP < o.F || o.dtype < 0 || o.dtype > 1 || o.channel < 0 || o.channel > 1 ||
+                    (o.kind == 9 && !o.b)) return MSMC_E_SHAPE;
+                total = ((o.kind == 8 ? (long)o.B * o.F * o.T : (long)o.B * o.T * o.FP) + 3) / 4;      // (a lane owns four elements)
                 break;
             case 6: case 7:
                 if (o.R <= 0 || (o.kind == 7 && !o.b)) return MSMC_E_SHAPE;

@@ -70,7 +70,7 @@ class SpectralOp(ctypes.Structure):
     """msmc_spectral_op of include/msmc_hip.h."""
     _fields_ = [('kind', _i), ('dtype', _i), ('a', _vp), ('b', _vp), ('c', _vp), ('out', _vp),
                 ('B', _i), ('L', _i), ('T', _i), ('n_fft', _i), ('NP', _i), ('hop', _i), ('pad', _i),
-                ('F', _i), ('CP', _i), ('FP', _i), ('clamp_mode', _i), ('lo', _f), ('R', ctypes.c_long)]
+                ('F', _i), ('CP', _i), ('FP', _i), ('clamp_mode', _i), ('lo', _f), ('R', ctypes.c_long), ('channel', _i)]
 
 
 SPECTRAL_MULTI_MAX = 8
@@ -101,6 +101,8 @@ _SIGNATURES.update({
     'msmc_mrd_image_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'msmc_mrd_image_fwd_dt': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'msmc_mrd_image_bwd_dt': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'msmc_mrd_image1_fwd_dt': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'msmc_mrd_image1_bwd_dt': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'msmc_wave_fan_fwd': (_i, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _i, _i, _i, _vp]),
     'msmc_wave_fan_bwd': (_i, [ctypes.POINTER(_vp), _i, ctypes.POINTER(_vp), ctypes.POINTER(_i), _i, _vp, _i, _i, _i, _vp]),
     'msmc_log_clamp_fwd': (_i, [_vp, _vp, ctypes.c_long, _f, _vp]),

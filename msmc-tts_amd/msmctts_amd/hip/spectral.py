@@ -84,16 +84,43 @@ class _SpecMag(torch.autograd.Function):
 
 _IMG_DT = {torch.float32: 0, torch.bfloat16: 1}
 
+# mrd_config.domain (reference hifigan/discriminator.py:79-116, audio.py:410-419) -> channel the image kernels write: None = the
+# two-channel (magnitude, log-magnitude) image, 0 / 1 = that channel alone (csrc/spectral.hip mrd_image1_*)
+DOMAINS = {'double': None, 'linear': 0, 'log': 1}
+
+
+def domain_channel(domain):
+    if domain not in DOMAINS:
+        raise ValueError('unknown spectral domain %r (one of %s)' % (domain, ', '.join(sorted(DOMAINS))))
+    return DOMAINS[domain]
+
+
+def _image_fwd(mel, img, B, T, F, FP, channel, dtype, stream):
+    if channel is None:
+        lib.check(lib.get().msmc_mrd_image_fwd_dt(lib.ptr(mel), lib.ptr(img), B, T, F, FP, _IMG_DT[dtype], stream), 'msmc_mrd_image_fwd_dt')
+    else:
+        lib.check(lib.get().msmc_mrd_image1_fwd_dt(lib.ptr(mel), lib.ptr(img), B, T, F, FP, channel, _IMG_DT[dtype], stream),
+                  'msmc_mrd_image1_fwd_dt')
+
+
+def _image_bwd(mel, g, gm, B, T, F, FP, channel, dtype, stream):
+    if channel is None:
+        lib.check(lib.get().msmc_mrd_image_bwd_dt(lib.ptr(mel), lib.ptr(g), lib.ptr(gm), B, T, F, FP, _IMG_DT[dtype], stream),
+                  'msmc_mrd_image_bwd_dt')
+    else:
+        lib.check(lib.get().msmc_mrd_image1_bwd_dt(lib.ptr(mel), lib.ptr(g), lib.ptr(gm), B, T, F, FP, channel, _IMG_DT[dtype], stream),
+                  'msmc_mrd_image1_bwd_dt')
+
 
 class _MrdImage(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mel, F, dtype=torch.float32):
+    def forward(ctx, mel, F, dtype=torch.float32, domain='double'):
         B, _, T, FP = mel.shape
-        img = torch.empty((B, F, T, 2), dtype=dtype, device=mel.device)
-        lib.check(lib.get().msmc_mrd_image_fwd_dt(lib.ptr(mel), lib.ptr(img), B, T, F, FP, _IMG_DT[dtype], lib.stream(mel)),
-                  'msmc_mrd_image_fwd_dt')
+        ch = domain_channel(domain)
+        img = torch.empty((B, F, T, 2 if ch is None else 1), dtype=dtype, device=mel.device)
+        _image_fwd(mel, img, B, T, F, FP, ch, dtype, lib.stream(mel))
         ctx.save_for_backward(mel)
-        ctx.F, ctx.dtype = F, dtype
+        ctx.F, ctx.dtype, ctx.channel = F, dtype, ch
         return img
 
     @staticmethod
@@ -104,9 +131,8 @@ class _MrdImage(torch.autograd.Function):
         if g.dtype != ctx.dtype:
             g = g.to(ctx.dtype)
         gm = torch.empty_like(mel)
-        lib.check(lib.get().msmc_mrd_image_bwd_dt(lib.ptr(mel), lib.ptr(g), lib.ptr(gm), B, T, ctx.F, FP, _IMG_DT[ctx.dtype],
-                                                  lib.stream(g)), 'msmc_mrd_image_bwd_dt')
-        return gm, None, None
+        _image_bwd(mel, g, gm, B, T, ctx.F, FP, ctx.channel, ctx.dtype, lib.stream(g))
+        return gm, None, None, None
 
 
 class _LogClamp(torch.autograd.Function):
@@ -209,9 +235,10 @@ class MrdFront(object):
     transformed: the front-end has no parameters -- reuses the image and back-propagates through its rows only
     (``image_rows``) instead of recomputing 25 launches per pass."""
 
-    def __init__(self, x, n_fft, hop, dft, fb, dtype, split=None):
+    def __init__(self, x, n_fft, hop, dft, fb, dtype, split=None, domain='double'):
         B, L = x.shape
         self.B, self.L, self.n_fft, self.hop, self.dft, self.fb, self.dtype = B, L, n_fft, hop, dft, fb, dtype
+        self.domain, self.channel = domain, domain_channel(domain)
         # constant-matrix GEMMs in split bf16 (2^-16 relative) when the stack computes in bf16, exact fp32 otherwise
         self.split = split = (dtype == torch.bfloat16 and SPLIT_BF16) if split is None else bool(split)
         F = self.F = n_fft // 2 + 1
@@ -230,9 +257,8 @@ class MrdFront(object):
         lib.check(Lb.msmc_spec_mag_fwd(lib.ptr(self.spec), lib.ptr(self.mag), B * T, F, CP, FP, 1e-7, 1, lib.stream(xc)),
                   'msmc_spec_mag_fwd')
         self.mel = _const_gemm(self.mag, fb[0], geom, split) if fb is not None else self.mag
-        self.img = torch.empty((B, F, T, 2), dtype=dtype, device=x.device)
-        lib.check(Lb.msmc_mrd_image_fwd_dt(lib.ptr(self.mel), lib.ptr(self.img), B, T, F, FP, _IMG_DT[dtype], lib.stream(xc)),
-                  'msmc_mrd_image_fwd_dt')
+        self.img = torch.empty((B, F, T, 2 if self.channel is None else 1), dtype=dtype, device=x.device)
+        _image_fwd(self.mel, self.img, B, T, F, FP, self.channel, dtype, lib.stream(xc))
 
     def image(self, r0, r1):
         """rows r0 .. r1-1 of the image: a view where the kernels can take it (16-byte aligned -- any row offset that is a
@@ -250,8 +276,7 @@ class MrdFront(object):
             g = g.to(self.dtype)
         mel, mag, spec = self.mel[r0:r1], self.mag[r0:r1], self.spec[r0:r1]
         gm = torch.empty_like(mel)
-        lib.check(Lb.msmc_mrd_image_bwd_dt(lib.ptr(mel), lib.ptr(g), lib.ptr(gm), b, T, F, FP, _IMG_DT[self.dtype],
-                                           lib.stream(g)), 'msmc_mrd_image_bwd_dt')
+        _image_bwd(mel, g, gm, b, T, F, FP, self.channel, self.dtype, lib.stream(g))
         geom = _geom1(T)
         if self.fb is not None:
             gm = _const_gemm(gm, self.fb[1], geom, self.split, dgrad=True)
@@ -300,8 +325,10 @@ def _gemms(xs, ws, split, dgrad=False):
     return [_const_gemm(x, w, _geom1(x.shape[2]), False, dgrad=dgrad) for x, w in zip(xs, ws)]
 
 
-def mrd_fronts(x, specs, dtype, split=None):
-    """``MrdFront(x, n_fft, hop, dft, fb, dtype)`` for every (n_fft, hop, dft, fb) of ``specs``, all chains advancing together"""
+def mrd_fronts(x, specs, dtype, split=None, domain='double'):
+    """``MrdFront(x, n_fft, hop, dft, fb, dtype, domain=domain)`` for every (n_fft, hop, dft, fb) of ``specs``, all chains advancing
+    together"""
+    channel = domain_channel(domain)
     fronts = [MrdFront.__new__(MrdFront) for _ in specs]
     B, L = x.shape
     xc = x.detach().contiguous().float()
@@ -310,6 +337,7 @@ def mrd_fronts(x, specs, dtype, split=None):
     frs, ops = [], []
     for f, (n_fft, hop, dft, fb) in zip(fronts, specs):
         f.B, f.L, f.n_fft, f.hop, f.dft, f.fb, f.dtype, f.split = B, L, n_fft, hop, dft, fb, dtype, split
+        f.domain, f.channel = domain, channel
         f.F, f.T = n_fft // 2 + 1, L // hop + 1
         lo, n_eff = dft[2], dft[3]
         f.frame_args = (f.T, n_eff, _pad4(n_eff), hop, n_fft // 2 - lo)
@@ -331,8 +359,9 @@ def mrd_fronts(x, specs, dtype, split=None):
     for f in fronts:
         if f.fb is None:
             f.mel = f.mag
-        f.img = torch.empty((B, f.F, f.T, 2), dtype=dtype, device=x.device)
-        ops.append(_op(4, st, f.mel, f.img, dtype=_IMG_DT[dtype], B=B, T=f.T, F=f.F, FP=_pad4(f.F)))
+        f.img = torch.empty((B, f.F, f.T, 2 if channel is None else 1), dtype=dtype, device=x.device)
+        ops.append(_op(4, st, f.mel, f.img, dtype=_IMG_DT[dtype], B=B, T=f.T, F=f.F, FP=_pad4(f.F)) if channel is None else
+                   _op(8, st, f.mel, f.img, dtype=_IMG_DT[dtype], B=B, T=f.T, F=f.F, FP=_pad4(f.F), channel=channel))
     _multi(ops)
     return fronts
 
@@ -353,7 +382,8 @@ def backward_rows_lockstep(fronts, gs, r0, r1):
         mel = f.mel[r0:r1]
         gm = torch.empty_like(mel)
         gms.append(gm)
-        ops.append(_op(5, st, mel, gm, b=g, dtype=_IMG_DT[f.dtype], B=b, T=f.T, F=f.F, FP=f.mag.shape[-1]))
+        ops.append(_op(5, st, mel, gm, b=g, dtype=_IMG_DT[f.dtype], B=b, T=f.T, F=f.F, FP=f.mag.shape[-1]) if f.channel is None else
+                   _op(9, st, mel, gm, b=g, dtype=_IMG_DT[f.dtype], B=b, T=f.T, F=f.F, FP=f.mag.shape[-1], channel=f.channel))
     _multi(ops)
     with_fb = [i for i, (f, _) in enumerate(live) if f.fb is not None]
     if with_fb:
@@ -406,15 +436,15 @@ class _MrdImage2(torch.autograd.Function):
     """the whole chain as ONE autograd node: forward = MrdFront(x), backward = MrdFront.backward_rows over all rows"""
 
     @staticmethod
-    def forward(ctx, x, n_fft, hop, dft, fb, dtype):
-        ctx.front = MrdFront(x, n_fft, hop, dft, fb, dtype)
+    def forward(ctx, x, n_fft, hop, dft, fb, dtype, domain):
+        ctx.front = MrdFront(x, n_fft, hop, dft, fb, dtype, domain=domain)
         img, ctx.front.img = ctx.front.img, None         # (the node must not hold its own output: a reference cycle)
         return img
 
     @staticmethod
     def backward(ctx, g):
         f = ctx.front
-        return f.backward_rows(g, 0, f.B), None, None, None, None, None
+        return f.backward_rows(g, 0, f.B), None, None, None, None, None, None
 
 
 class _MrdImageRows(torch.autograd.Function):
@@ -432,16 +462,17 @@ class _MrdImageRows(torch.autograd.Function):
         return ctx.front.backward_rows(g, *ctx.rows), None, None, None
 
 
-def mrd_image(x, n_fft, hop, dft, fb, dtype=torch.float32):
-    """x (B, L) -> MRD input image, channels-last [B, F, T', 2] (ch0 mel-scaled magnitude, ch1 normalised log), written
-    in ``dtype`` (the discriminator stack's compute dtype: the spectra themselves stay fp32)."""
-    return _MrdImage2.apply(x, n_fft, hop, dft, fb, dtype)
+def mrd_image(x, n_fft, hop, dft, fb, dtype=torch.float32, domain='double'):
+    """x (B, L) -> MRD input image, channels-last [B, F, T', C], written in ``dtype`` (the discriminator stack's compute dtype: the
+    spectra themselves stay fp32).  ``domain`` 'double': C = 2 (ch0 mel-scaled magnitude, ch1 normalised log); 'linear' / 'log':
+    C = 1, that channel alone (``fb`` None: the magnitude is not mel-projected)."""
+    return _MrdImage2.apply(x, n_fft, hop, dft, fb, dtype, domain)
 
 
-def mrd_front(x, n_fft, hop, dft, fb, dtype=torch.float32):
+def mrd_front(x, n_fft, hop, dft, fb, dtype=torch.float32, domain='double'):
     """the same evaluation as an object whose image (``.img``) and intermediates outlive the call (no autograd: for
     waveforms without gradient history -- the D step's detached batch)"""
-    return MrdFront(x, n_fft, hop, dft, fb, dtype)
+    return MrdFront(x, n_fft, hop, dft, fb, dtype, domain=domain)
 
 
 def mrd_image_rows(x, front, r0, r1):

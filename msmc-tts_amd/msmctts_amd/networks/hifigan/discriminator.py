@@ -56,7 +56,7 @@ class DiscriminatorR(nn.Module):
         return [st._modules[st.key].hip_layer() for st in self.discriminator]
 
     def forward_hip(self, bank, layers, img, dtype):
-        """img channels-last [B, F, T', 2] -> (score (B, 1, F'', T''), 6 activated feature maps as NCHW-shaped views)."""
+        """img channels-last [B, F, T', C] (C = 2, or 1 for the 'linear' / 'log' domains) -> (score (B, 1, F'', T''), 6 activated feature maps as NCHW-shaped views)."""
         x = img.to(dtype)
         fmaps = []
         last = len(layers) - 1
@@ -78,12 +78,11 @@ class MultiResolutionDiscriminator(nn.Module):
         self.stfts = nn.ModuleList([
             TorchSTFT(fft_size=h * 4, hop_size=h, win_size=h * 4, normalized=True, domain=domain,
                       mel_scale=mel_scale, sample_rate=sample_rate) for h in hop_lengths])
-        self.domain = domain
+        self.domain = domain          # (an unknown domain: ValueError from TorchSTFT above)
         self.discriminators = nn.ModuleList([DiscriminatorR(2 if domain == 'double' else 1, c)
                                              for _, c in zip(hop_lengths, hidden_channels)])
 
     def thunks(self, bank, layers, x, dtype):
-        assert self.domain == 'double', 'every shipped config uses the two-channel (mag, log-mag) image'
         wav = x.squeeze(1) if x.dim() == 3 else x
         return [lambda stft=stft, disc=disc, ls=ls: disc.forward_hip(bank, ls, stft.image_cl(wav, dtype), dtype)
                 for stft, disc, ls in zip(self.stfts, self.discriminators, layers)]
@@ -215,7 +214,8 @@ class Discriminator(nn.Module):
         if spectral.FRONTS_LOCKSTEP:          # every stage of the five chains in one launch (hip/spectral.py mrd_fronts)
             with torch.autocast(device_type=wav.device.type, enabled=False):
                 specs = [(stft.fft_size, stft.hop_size) + tuple(stft.consts(wav.device)) for stft in self.mrd.stfts]
-                return SpectralFronts(spectral.mrd_fronts(wav.detach().float(), specs, self.hip_dtype), 0, wav.shape[0])
+                return SpectralFronts(spectral.mrd_fronts(wav.detach().float(), specs, self.hip_dtype, domain=self.mrd.domain),
+                                      0, wav.shape[0])
         return SpectralFronts([stft.front(wav.detach(), self.hip_dtype) for stft in self.mrd.stfts], 0, wav.shape[0])
 
     def forward(self, y, fronts=None):
@@ -236,7 +236,6 @@ class Discriminator(nn.Module):
         """The sub-discriminators advance layer by layer: layer i of all six resolution (all five period) stacks is ONE
         grouped launch (hip_conv_group) -- each of them alone is a grid of tens to hundreds of workgroups."""
         dtype = self.hip_dtype
-        assert self.mrd.domain == 'double', 'every shipped config uses the two-channel (mag, log-mag) image'
         wav = y.squeeze(1)
         # ONE launch makes the period stacks' inputs (cast + reflection pad to a multiple of the period) and hands the
         # resolution stacks' front-ends aliases of the waveform; its backward launch sums all ten consumers' gradients

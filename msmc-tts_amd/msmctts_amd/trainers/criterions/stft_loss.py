@@ -97,7 +97,9 @@ class STFTLoss(nn.Module):
 
     def __init__(self, fft_size, hop_size, win_size, mel_scale=False, sample_rate=24000):
         super().__init__()
-        assert not mel_scale, 'mel-scaled MR-STFT is not used by any shipped config'
+        assert not mel_scale, ('mel-scaled MR-STFT is not used by any shipped config, and is not mirrored: the reference hands MelScale a '
+                               "(B, T', F) magnitude while MelScale.forward takes dim -2 as frequency, so its filter bank is built for "
+                               "n_freqs = T', mixes time frames and is cached at the first batch's length")
         self.fft_size, self.hop_size, self.win_size = fft_size, hop_size, win_size
         self._cache = {}
 

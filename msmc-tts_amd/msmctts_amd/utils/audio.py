@@ -62,6 +62,8 @@ class TorchSTFT(nn.Module):
         self.fft_size, self.hop_size, self.win_size = fft_size, hop_size, win_size
         self.ref_level_db, self.min_level_db = ref_level_db, min_level_db
         self.normalized, self.domain = normalized, domain
+        if domain not in ('double', 'linear', 'log'):
+            raise ValueError("unknown spectral domain %r (one of 'double', 'linear', 'log')" % (domain,))
         assert (ref_level_db, min_level_db) == (20, -100), 'the image kernel fixes the reference levels'
         self.mel_scale = MelScale(n_mels=fft_size // 2 + 1, sample_rate=sample_rate,
                                   n_stft=fft_size // 2 + 1) if mel_scale else None
@@ -85,11 +87,12 @@ class TorchSTFT(nn.Module):
         return self._consts[key]
 
     def image_cl(self, x, dtype=torch.float32):
-        """x (B, L) -> channels-last [B, F, T', 2] in ``dtype``: ch0 (mel-scaled) magnitude, ch1 normalised log-magnitude."""
+        """x (B, L) -> channels-last [B, F, T', C] in ``dtype``.  Domain 'double': C = 2, ch0 (mel-scaled) magnitude, ch1 normalised
+        log-magnitude; 'linear' / 'log': C = 1, the magnitude / the normalised log-magnitude alone."""
         from ..hip import spectral
         dft, fb = self.consts(x.device)
         with torch.autocast(device_type=x.device.type, enabled=False):
-            return spectral.mrd_image(x.float(), self.fft_size, self.hop_size, dft, fb, dtype)
+            return spectral.mrd_image(x.float(), self.fft_size, self.hop_size, dft, fb, dtype, self.domain)
 
     def front(self, x, dtype=torch.float32):
         """the same evaluation kept as an object (hip/spectral.py MrdFront): its image and intermediates can serve a later
@@ -97,13 +100,11 @@ class TorchSTFT(nn.Module):
         from ..hip import spectral
         dft, fb = self.consts(x.device)
         with torch.autocast(device_type=x.device.type, enabled=False):
-            return spectral.mrd_front(x.float(), self.fft_size, self.hop_size, dft, fb, dtype)
+            return spectral.mrd_front(x.float(), self.fft_size, self.hop_size, dft, fb, dtype, self.domain)
 
     def transform(self, x):
-        img = self.image_cl(x)                       # [B, F, T, 2]
-        B, F, T, _ = img.shape
-        if self.domain == 'linear':
-            return img[..., 0], None
-        if self.domain == 'log':
-            return img[..., 1], None
+        img = self.image_cl(x)                       # [B, F, T, C]
+        B, F, T, C = img.shape
+        if C == 1:                                   # 'linear' / 'log': the one channel the kernels wrote
+            return img.reshape(B, F, T), None
         return img.permute(0, 3, 1, 2).reshape(B, 2 * F, T), None
