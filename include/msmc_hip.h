@@ -443,6 +443,20 @@ int msmc_spectral_multi(const msmc_spectral_op* ops, int n, msmc_stream stream);
  * starts[b] * hop + nframes * hop <= L (VQGANTrainer checks the batch on the host). */
 int msmc_window_gather(const long* starts, const float* wav, long* frames, float* target, int B, int nframes, int hop, long L,
                        msmc_stream stream);
+/* Windows of a SUBSET of utterances (reference emb_vqgan_trainer.py:41-56: n <= B sampled utterances, one window each), csrc/window.hip.
+ * x [B][T][C], win [n][2] int32 on the device = (utterance u_j, first row s_j), out [n][W][C] -- the channels-last [n, 1, W, C]
+ * image a convolution stack reads; *_bf16: 0 = fp32, 1 = bf16 for that tensor.  out[j][t][c] = x[u_j][s_j + t][c], converted
+ * with round-to-nearest-even (the bits of torch.Tensor.to); a row s_j + t outside [0, T) or an utterance outside [0, B) is never
+ * read and gives zeros, so any table contents are safe.
+ * Backward: EVERY element of gx [B][T][C] is written exactly once with plain stores -- gout of the window row that covers it,
+ * zero otherwise (no atomics, no zero-fill launch before it).  Caller's contract: the u_j are strictly increasing; when broken,
+ * which window wins is unspecified but no access leaves the buffers.
+ * C % 8 == 0 (and 16-byte aligned pointers): 16-byte accesses; any other C >= 1: one element per access.
+ * MSMC_E_SHAPE (nothing is launched) for W < 1, n < 1, n > B, C < 1, T < 1. */
+int msmc_window_gather_fwd(const void* x, int x_bf16, const int* win, void* out, int out_bf16, int B, int T, int C, int n, int W,
+                           msmc_stream stream);
+int msmc_window_gather_bwd(const void* gout, int gout_bf16, const int* win, void* gx, int gx_bf16, int B, int T, int C, int n, int W,
+                           msmc_stream stream);
 
 /* y = log(max(x, lo)) and its backward gx = g * (x > lo ? 1/x : 0) over n elements (stft_loss.py:110-114). */
 int msmc_log_clamp_fwd(const float* x, float* y, long n, float lo, msmc_stream stream);

@@ -60,6 +60,7 @@ class DeviceLoader(object):
     def _upload(self, batch):
         batch = self._static(dict(batch))
         host_lengths = batch['mel_length'].tolist() if 'mel_length' in batch else None
+        host_emb_lengths = batch['emb_length'].tolist() if 'emb_length' in batch else None      # (EmbVQGANTrainer samples from these)
         if self.stream is None:
             out = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
         else:
@@ -68,6 +69,8 @@ class DeviceLoader(object):
                            else v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()}
         if host_lengths is not None:
             out['mel_length_host'] = host_lengths
+        if host_emb_lengths is not None:
+            out['emb_length_host'] = host_emb_lengths
         return out
 
     def __iter__(self):

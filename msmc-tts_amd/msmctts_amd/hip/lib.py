@@ -93,6 +93,8 @@ class TensorTable(ctypes.Structure):
 _SIGNATURES.update({
     'msmc_spectral_multi': (_i, [ctypes.POINTER(SpectralOp), _i, _vp]),
     'msmc_window_gather': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_long, _vp]),
+    'msmc_window_gather_fwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'msmc_window_gather_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'msmc_stft_frames_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'msmc_stft_frames_bwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'msmc_spec_mag_fwd': (_i, [_vp, _vp, ctypes.c_long, _i, _i, _i, _f, _i, _vp]),

@@ -20,6 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ...hip import norm as hipnorm
+from ...hip import window as hipwindow
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
 from .msmc_vqgan import MultiStageQuantizer, PriorPredictor, _fft_pos
@@ -103,9 +104,33 @@ class MSMCVQGANEmb(nn.Module):
             x, _ = self.frame_decoder(x, _fft_pos(lengths, x), lengths=lengths)
         return x
 
-    def forward(self, emb, emb_length, pitch=None, energy=None, mel=None, ref=None, window='full'):
+    def _window(self, dec_in, window, window_frames):
+        """the vocoder's input frames for ``window`` (see ``forward``).  On the GPU (or with the interpreter build bound) the
+        (utterance, start) table and the reference's triples of equal length run hip/window.py's ``window_gather``: one launch
+        into the generator's compute dtype and channels-last layout, one launch for the gradient -- the same values as the
+        slice / stack / cast chain, which every other form keeps"""
+        if window_frames is not None:
+            if not (torch.is_tensor(window) and window.dim() == 2 and window.shape[1] == 2 and window.dtype == torch.int32):
+                raise TypeError('window_frames goes with an int32 [n, 2] tensor of (utterance, start) pairs')
+            return hipwindow.window_gather(dec_in, window, int(window_frames), self.decoder.hip_dtype)
+        if torch.is_tensor(window):
+            return torch.gather(dec_in, 1, window.unsqueeze(-1).expand(-1, -1, dec_in.shape[-1]))
+        if isinstance(window, (list, tuple)):
+            if hipwindow.usable(dec_in) and len(window) > 0:
+                B, T = dec_in.shape[:2]
+                W = window[0][2] - window[0][1]
+                us = [i for i, _, _ in window]
+                if (W >= 1 and all(0 <= i < B and 0 <= s and e - s == W and e <= T for i, s, e in window)
+                        and all(b > a for a, b in zip(us, us[1:]))):
+                    return hipwindow.window_gather(dec_in, [(i, s) for i, s, _ in window], W, self.decoder.hip_dtype)
+            return torch.stack([dec_in[i, s:e] for i, s, e in window], dim=0)
+        return dec_in
+
+    def forward(self, emb, emb_length, pitch=None, energy=None, mel=None, ref=None, window='full', window_frames=None):
         """``window``: None = no waveform (frames only), 'full' = decode every frame, a list of (utterance, start, end)
-        frame triples (the reference's convention here, :206-209) or a [B, n] tensor of frame indices = decode those"""
+        frame triples (the reference's convention here, :206-209) or a [B, n] tensor of frame indices = decode those; with
+        ``window_frames`` = W, an int32 [n, 2] device tensor of (utterance, start) pairs = decode W frames from each start
+        (strictly increasing utterance indices; frames past the end read as zeros)"""
         if self.training:
             hipnorm.advance_seed(emb.device)        # fresh dropout masks for the fused kernels of this step
         enc, content = self.encoder(self.in_linear(emb), emb_length, pitch, energy)
@@ -118,10 +143,7 @@ class MSMCVQGANEmb(nn.Module):
         if hasattr(self, 'mel_predictor'):
             out['mel_outputs'] = self.mel_predictor(dec_in)
         if window is not None:
-            if torch.is_tensor(window):
-                dec_in = torch.gather(dec_in, 1, window.unsqueeze(-1).expand(-1, -1, dec_in.shape[-1]))
-            elif isinstance(window, (list, tuple)):
-                dec_in = torch.stack([dec_in[i, s:e] for i, s, e in window], dim=0)
+            dec_in = self._window(dec_in, window, window_frames)
             out['decoder_outputs'] = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
         return out
 

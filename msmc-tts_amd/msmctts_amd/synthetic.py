@@ -22,6 +22,29 @@ def make_batch(batch_size=16, frames=400, in_dim=80, hop=300, seed=1234, rank=0,
     return {k: v.to(device) for k, v in batch.items()}
 
 
+def make_emb_batch(batch_size=16, frames=400, emb_dim=1024, mel_dim=80, hop=200, seed=1234, rank=0, device='cpu'):
+    """The contract of ``EmbDataset.collate_fn`` (``EmbVQGANTrainer.train_step``'s batch): ``emb (B,T,emb_dim)`` ~ N(0,1) with
+    padding 0, ``emb_length (B,) int64`` sorted descending with ``max == T``, ``mel (B,T,mel_dim)`` ~ N(0,1) with padding -4,
+    ``wav (B, T*hop, 1)`` ~ U(-1,1) with padding 0, ``wav_length = emb_length * hop``; ``emb_length_host`` is the host list of
+    the lengths the trainer samples its windows from (a loader hands it along; reading ``emb_length`` back would be a sync)."""
+    g = torch.Generator().manual_seed(seed + rank)
+    lengths = torch.randint(frames // 2, frames + 1, (batch_size,), generator=g)
+    lengths[0] = frames
+    lengths = torch.sort(lengths, descending=True).values.to(torch.int64)
+    emb = torch.randn(batch_size, frames, emb_dim, generator=g)
+    mel = torch.randn(batch_size, frames, mel_dim, generator=g)
+    wav = torch.rand(batch_size, frames * hop, 1, generator=g) * 2 - 1
+    valid = torch.arange(frames)[None, :, None] < lengths[:, None, None]
+    emb = torch.where(valid, emb, torch.zeros_like(emb))
+    mel = torch.where(valid, mel, torch.full_like(mel, -4.0))
+    s = torch.arange(frames * hop)[None, :, None]
+    wav = torch.where(s < (lengths * hop)[:, None, None], wav, torch.zeros_like(wav))
+    batch = {'emb': emb, 'emb_length': lengths, 'mel': mel, 'wav': wav, 'wav_length': lengths * hop}
+    batch = {k: v.to(device) for k, v in batch.items()}
+    batch['emb_length_host'] = lengths.tolist()
+    return batch
+
+
 def make_text_batch(mel_length, n_symbols=(100, 10, 2), phonemes=(30, 56), seed=4321, rank=0, device='cpu'):
     """The text side of a ``TTSDataset`` batch (reference msmctts/datasets/tts_dataset.py) for the given mel lengths:
     ``text (B, P, 3)`` symbol / tone / boundary ids (0 = padding), ``text_length (B,)``, ``dur (B, P)`` whole-frame durations of

@@ -64,5 +64,16 @@ class MSMCTTS(BaseTask):
             self.predictor.autoencoder = self.autoencoder
 
 
+class NASynTTSEmb(MSMCTTS):
+    """``task._name: NASynTTSEmb`` of the QS-TTS synthesiser YAML.  The reference tree names this class but does not ship it; it
+    is defined by what ``EmbVQGANTrainer`` and ``MSMCVQGANEmb`` consume: the same container (children ``autoencoder``,
+    ``discriminator``), analysis-synthesis over speech-embedding frames."""
+
+    def analysis_synthesis(self, input_dict):
+        """emb (B, T, emb_dim) + emb_length (+ pitch, energy, ref) -> {'wav': (B, T * hop)}"""
+        out = self.autoencoder(**{k: v for k, v in input_dict.items() if k in ('emb', 'emb_length', 'pitch', 'energy', 'ref')})
+        return {'wav': out['decoder_outputs'].squeeze(-1)}
+
+
 class TTS(MSMCTTS):
     """``task._name: TTS`` resolves to the same container (its acoustic-model + vocoder pipeline is out of scope)."""

@@ -171,12 +171,21 @@ class VQGANTrainer(BaseTrainer):
     # Eagerly they run back to back; ``use_graphs`` captures each into a hipGraph (static batch buffers,
     # window indices on the device) and replays them with the RCCL all-reduces in between.
     # ------------------------------------------------------------------------------------------
+    # the two places a subclass with another autoencoder call or phase table differs (EmbVQGANTrainer)
+    def _autoencode(self, st):
+        """the autoencoder's training forward of this step -> its output dictionary"""
+        return self.model.autoencoder(st.mel, st.mel_length, warmup=st.phase == 0, window=st.frame_window)
+
+    def _spectral_on(self, st):
+        """whether the spectral loss is taken in this step's phase (here: together with the adversarial terms)"""
+        return st.phase == 2
+
     def _segment_a(self, st):
         losses = st.losses = {}
         mel, mel_length = st.mel, st.mel_length
-        ae, disc = self.model.autoencoder, getattr(self.model, 'discriminator', None)
+        disc = getattr(self.model, 'discriminator', None)
         with self._amp():
-            out = ae(mel, mel_length, warmup=st.phase == 0, window=st.frame_window)
+            out = self._autoencode(st)
         vq = self.vq_criterion(out)
         losses.update(vq)
         g_loss = vq['vq_loss']
@@ -192,7 +201,7 @@ class VQGANTrainer(BaseTrainer):
             g_terms, g_weights = [g_loss, ml], [1.0, self.lambda_frame]
         else:
             g_terms, g_weights = [g_loss], [1.0]
-        if st.phase < 2:
+        if not self._spectral_on(st):
             st.g_loss = hiploss.weighted_sum(g_terms, g_weights) if len(g_terms) > 1 else g_loss
             return
         st.predict = predict = out['decoder_outputs'].squeeze(-1).float()
@@ -205,6 +214,10 @@ class VQGANTrainer(BaseTrainer):
                     losses[name] = term
                 stl = sum(stl.values())
             return stl
+        if st.phase < 2:                    # (a phase with the spectral loss but no adversarial terms: no discriminator pass)
+            losses['stft_loss'] = stl = spectral_loss()
+            st.g_loss = hiploss.weighted_sum(g_terms + [stl], g_weights + [self.lambda_stft])
+            return
         # the spectral loss has no consumer before the generator step: a side branch under the discriminator step (its
         # backward nodes replay on the same stream, next to the generator step's D(fake) backward)
         side = (hipconvnet.own_streams(predict.device, 1, 'loss-fork') if (self.loss_fork and predict.is_cuda
