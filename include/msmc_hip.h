@@ -57,10 +57,21 @@ int msmc_vq_prepare(const float* embed, float* embed_t, float* enorm, int H, int
 /* Search + gather + straight-through value + head-averaged squared error, all heads, one launch.
  *   dist = (|x|^2 - 2 x.e_k) + |e_k|^2 in fp32, first-minimum tie rule   (modules.py:26-31)
  *   quant[n] = x + (e_best - x) ; diff[n] = (sum_h (e_best - x_h)^2) / H  (modules.py:33,59-60,147)
- * Requires d % 4 == 0, K % 16 == 0, one head's transposed codebook <= 80 KiB of LDS.
- * quant may alias x.  Returns MSMC_E_SHAPE otherwise. */
+ * Requires d % 4 == 0 and K % 16 == 0 (MSMC_E_SHAPE otherwise).  Where at least one head's transposed codebook fits LDS
+ * (160 KiB) it stays resident; larger codebooks take the streamed kernel below (chunk chosen by the launcher), which
+ * additionally needs N * D * 4 < 2^32 and d <= 848.  quant may alias x. */
 int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
                    int64_t* ind, int N, int D, int H, int K, msmc_stream stream);
+
+/* The same search with no resident codebook (msmc-tts_amd/csrc/vq_stream.inc): every head's codebook passes through LDS
+ * in double-buffered chunks of `chunk` codewords while a wave keeps its 16 frames and a running first minimum.  Same
+ * distance expression, same fp32 summation order over the d channels, same tie rule: on every shape msmc_vq_search
+ * serves with a resident kernel, quant, diff and ind are bit-identical to it.  chunk = 0: the launcher's choice (the
+ * largest multiple of 16 that keeps a workgroup at or under 80 KiB of LDS, else under 160 KiB); chunk > 0: forced (a
+ * multiple of 16, at most 256; larger than K means K).  Returns MSMC_E_SHAPE for d % 4, K % 16, a chunk that is not a
+ * multiple of 16 or does not fit, N * D * 4 >= 2^32; 0 at once for N == 0.  quant may alias x. */
+int msmc_vq_search_stream(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
+                          int64_t* ind, int N, int D, int H, int K, int chunk, msmc_stream stream);
 
 /* The same search -- identical indices, quant and diff, bit for bit -- under the HBM roof for K >= 64
  * (msmc-tts_amd/csrc/vq_shortlist.inc): all K distances approximately on the bf16 matrix cores (two-piece bf16 splits of

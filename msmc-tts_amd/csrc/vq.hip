@@ -12,6 +12,9 @@
 // gather, straight-through value and squared error are formed in LDS in place and written back
 // with full-row stores.  Algorithmic HBM bytes per frame: 4D (x) + 4D (quant) + 8H (ind) + 4D/H (diff).
 //
+// Codebooks too large to stay resident (one head beyond 160 KiB of LDS) take the streamed kernel of vq_stream.inc: same
+// distances, same summation order, same bits, the codebook passing through LDS in double-buffered chunks.
+//
 // msmc_vq_ema_update: deterministic two-stage reduction (per-tile counting sort of the indices in
 // LDS, ordered per-codeword sums, fixed-order reduction over tiles) then the EMA / Laplace
 // smoothing / renormalisation of the three buffers in place.
@@ -451,6 +454,7 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
 }
 
 #include "vq_shortlist.inc"
+#include "vq_stream.inc"
 
 typedef void (*vq_search_reg_fn)(const float*, const float*, const float*, float*, float*, int64_t*, int, int, int, int,
                                  int);
@@ -654,6 +658,7 @@ int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, flo
     const int d = D / H;
     if (d % 4 || K % 16 || K <= 0) return MSMC_E_SHAPE;
     if (N == 0) return 0;
+    const bool reg_family = d % 16 == 0 && vq_use_reg_kernel;
     if (d % 16 == 0 && vq_use_reg_kernel) {
         const int d4h = d / 16;
         vq_search_reg_fn rf = nullptr;
@@ -694,7 +699,8 @@ int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, flo
         if (L.total <= VQ_LDS_LIMIT) break;
         if (hpg > 1) { hpg = (hpg + 1) / 2; continue; }
         if (nw > 1) { nw >>= 1; hpg = H; continue; }
-        return MSMC_E_SHAPE;
+        // not even one head is resident with the narrowest workgroup: the codebook streams through LDS (vq_stream.inc)
+        return vq_stream_launch(x, embed_t, enorm, quant, diff, ind, N, D, H, K, 0, reg_family, stream);
     }
     const int nld = (VQ_TILE * (D / 4) + 63) / 64;
     vq_search_fn fn = nullptr;
@@ -714,6 +720,17 @@ int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, flo
                 ind, N, D, H, K, hpg, L);
     msmc_vq_last = msmc_prof_name("vq_search_kernel");
     return msmc_check_launch();
+}
+
+// ---- streamed search (vq_stream.inc) ---------------------------------------------------------------------------------
+int msmc_vq_search_stream(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
+                          int64_t* ind, int N, int D, int H, int K, int chunk, msmc_stream stream) {
+    if (N < 0 || H <= 0 || D <= 0 || D % H) return MSMC_E_SHAPE;
+    const int d = D / H;
+    if (d % 4 || K % 16 || K <= 0) return MSMC_E_SHAPE;
+    if (chunk < 0 || chunk % 16) return MSMC_E_SHAPE;
+    if (N == 0) return 0;
+    return vq_stream_launch(x, embed_t, enorm, quant, diff, ind, N, D, H, K, chunk, d % 16 == 0 && vq_use_reg_kernel, stream);
 }
 
 // ---- shortlist search (vq_shortlist.inc) ----------------------------------------------------------------------------

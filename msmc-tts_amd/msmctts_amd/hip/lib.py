@@ -27,6 +27,7 @@ _SIGNATURES = {
     'msmc_stream_destroy': (_i, [_vp]),
     'msmc_vq_prepare': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_vq_search': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'msmc_vq_search_stream': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'msmc_vq_shortlist_bytes': (_sz, [_i, _i, _i]),
     'msmc_vq_prepare_shortlist': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_vq_search_shortlist': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

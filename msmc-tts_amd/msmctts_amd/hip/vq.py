@@ -58,7 +58,7 @@ def _f32_frames(x):
 
 class _VQSearch(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, embed_t, enorm, image=None, force_shortlist=False):
+    def forward(ctx, x, embed_t, enorm, image=None, force_shortlist=False, stream_chunk=None):
         H, K, d = embed_t.shape
         D = H * d
         assert x.shape[-1] == D, (x.shape, embed_t.shape)
@@ -69,7 +69,11 @@ class _VQSearch(torch.autograd.Function):
         diff = torch.empty(xc.shape[:-1] + (d,), dtype=torch.float32, device=x.device)
         ind = torch.empty(xc.shape[:-1] + (H,), dtype=torch.int64, device=x.device)
         L = lib.get()
-        if image is not None and (force_shortlist or N * K >= SHORTLIST_MIN_WORK):
+        if stream_chunk is not None:
+            lib.check(L.msmc_vq_search_stream(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
+                                              lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, int(stream_chunk),
+                                              lib.stream(xc)), 'msmc_vq_search_stream')
+        elif image is not None and (force_shortlist or N * K >= SHORTLIST_MIN_WORK):
             lib.check(L.msmc_vq_search_shortlist(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
                                                  lib.ptr(image, torch.uint8), lib.ptr(quant), lib.ptr(diff), lib.ptr(ind),
                                                  lib.ptr(SLOW_COUNT, torch.int64), N, D, H, K, lib.stream(xc)),
@@ -91,7 +95,7 @@ class _VQSearch(torch.autograd.Function):
         D = xc.shape[-1]
         N = xc.numel() // D
         if g_quant is None and g_diff is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         if g_quant is None:
             g_quant = torch.zeros_like(xc)
         g_quant = g_quant.contiguous().float()
@@ -100,17 +104,22 @@ class _VQSearch(torch.autograd.Function):
         L = lib.get()
         lib.check(L.msmc_vq_backward(lib.ptr(g_quant), lib.ptr(g_diff), lib.ptr(xc), lib.ptr(quant), lib.ptr(gx),
                                      N, D, ctx.heads, lib.stream(xc)), 'msmc_vq_backward')
-        return gx.to(ctx.in_dtype), None, None, None, None
+        return gx.to(ctx.in_dtype), None, None, None, None, None
 
 
-def vq_search(x, embed_t, enorm, shortlist=None):
+def vq_search(x, embed_t, enorm, shortlist=None, stream_chunk=None):
     """x [..., D] -> (quant [..., D] straight-through, diff [..., d], ind [..., H] int64).  ``shortlist``: None = the
     product's choice (the shortlist kernel where ``vq_prepare`` attached an image and the problem is large enough),
-    True = the shortlist kernel whatever the size (it must have an image), False = the exact kernel."""
+    True = the shortlist kernel whatever the size (it must have an image), False = the exact kernel.  ``stream_chunk``:
+    None = the product's choice through ``msmc_vq_search`` (resident codebook where one head fits LDS, the streamed kernel of
+    csrc/vq_stream.inc where it does not); an int = ``msmc_vq_search_stream`` with that chunk of codewords (0 = the
+    launcher's choice) whatever the shape -- same bits, for tests and tools."""
+    if stream_chunk is not None:
+        return _VQSearch.apply(x, embed_t, enorm, None, False, int(stream_chunk))
     image = getattr(embed_t, 'shortlist_image', None) if (SHORTLIST if shortlist is None else shortlist) else None
     if shortlist and image is None:
         raise RuntimeError('msmc_vq_search_shortlist does not take this shape (vq_prepare attached no shortlist image to this codebook)')
-    return _VQSearch.apply(x, embed_t, enorm, image, bool(shortlist))
+    return _VQSearch.apply(x, embed_t, enorm, image, bool(shortlist), None)
 
 
 # The EMA update of a stage has no reader before the next step's search (the quantised values of this step came from the

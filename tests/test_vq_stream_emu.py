@@ -1,0 +1,60 @@
+"""CPU: the streamed exact codeword search (csrc/vq_stream.inc) on the kernel interpreter, through the C entries, hip/vq.py, the
+quantiser modules (cases and references: tests/_vqstreamcases.py; the same on the GPU, with the VQGANTrainer steps -- over a minute
+on the interpreter at the model width the large codebook needs: tests/test_gpu_vq_stream.py)."""
+import os
+import subprocess
+
+import pytest
+
+import _vqstreamcases as cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU = os.path.join(ROOT, 'tests', 'emu', 'libmsmc_emu.so')
+DEV = 'cpu'
+
+
+@pytest.fixture(scope='module', autouse=True)
+def emulator():
+    subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'tests', 'emu')])
+    from msmctts_amd.hip import lib
+    saved = (lib._lib, lib._host_pointers_ok)
+    lib.use_library_for_tests(EMU)
+    assert lib.backend() == 'emu'
+    yield
+    lib._lib, lib._host_pointers_ok = saved
+
+
+@pytest.mark.parametrize('s,n', cases.SAME_PARAMS, ids=cases.SAME_IDS)
+def test_forced_chunks_give_the_bits_of_the_resident_kernel(s, n):
+    cases.check_same_bits_as_resident(DEV, s, n)
+
+
+def test_lds_tile_family_gives_the_bits_of_the_lds_tile_kernel():
+    cases.check_lds_tile_family_same_bits(DEV)
+
+
+@pytest.mark.parametrize('H,d,K', [(1, 64, 64), (2, 128, 128)], ids=['H1 d64 K64', 'H2 d128 K128'])
+def test_first_minimum_holds_across_chunk_boundaries(H, d, K):
+    cases.check_first_minimum_across_chunks(DEV, H, d, K)
+
+
+@pytest.mark.parametrize('s,n', cases.LARGE_PARAMS, ids=cases.LARGE_IDS)
+def test_codebooks_larger_than_lds_match_float64(s, n):
+    cases.check_large_shape(DEV, s, n)
+
+
+@pytest.mark.parametrize('m', range(len(cases.MODULES)), ids=cases.MODULE_IDS)
+def test_quantiser_modules_with_a_large_codebook_match_the_restated_reference(m):
+    cases.check_module(DEV, m)
+
+
+def test_refused_arguments_and_the_empty_input():
+    cases.check_refusals(DEV)
+
+
+def test_wrapper_threads_the_chunk():
+    cases.check_wrapper_threads_the_chunk(DEV)
+
+
+def test_the_symbol_is_exported():
+    cases.check_feature_present()

@@ -14,7 +14,7 @@ ABLATE = int(os.environ.get('ABLATE', '0'))      # msmc_vq_set_shortlist_ablate 
 lib.get().msmc_vq_set_shortlist_ablate(ABLATE)
 print('ablate mask', ABLATE)
 NS = [int(v) for v in os.environ.get('NS', '1600,6400,25600,131072,1048576').split(',')]
-CFG = [(4, 64), (4, 256), (8, 512)]
+CFG = [(4, 64), (4, 256), (8, 512), (1, 512), (2, 512)]      # (the last two: no resident kernel, csrc/vq_stream.inc)
 print('%-10s %9s | %-22s %9s %8s | %-22s %9s %8s | same  rerank   research' % ('H x K', 'N', 'product', 'us', 'GB/s', 'exact', 'us', 'GB/s'))
 for H, K in CFG:
     D = 256
