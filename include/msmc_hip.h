@@ -531,6 +531,17 @@ int msmc_masked_mean_bwd(const void* a, const void* b, const void* lengths, int 
 int msmc_triple_loss(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp, int N,
                      int D, int H, int K, float margin, int mean, msmc_stream stream);
 
+/* The same loss with no resident codebook (msmc-tts_amd/csrc/triple_stream.inc): every head's rows and norms pass through LDS
+ * in double-buffered chunks of `chunk` codewords while a workgroup keeps its frames.  Same expressions and outputs; the order
+ * of every fp32 sum depends on (d, K) alone -- not on the chunk or the grid.  On every head shape msmc_triple_loss takes it is
+ * that kernel's (one lane per frame): lossh and gp are bit-identical to it.  Beyond those shapes a frame's channels are split
+ * over L lanes (4 for d = 128, 8 for d = 256 / 512) and the active rows are added in blocks of 8 codewords with compensated block sums.  d = D/H in {16, 32, 64, 128, 256, 512}, any K >= 1.  chunk = 0: the launcher's choice (the largest
+ * multiple of 8 that keeps the two buffers under 80 KiB, at most 64); chunk > 0: forced (larger than K means K).  Returns
+ * MSMC_E_SHAPE for another d, p / embed_t / gp not 16-byte aligned, chunk < 0 or two buffers of 2 chunk (d + 1) floats beyond
+ * 160 KiB; 0 at once, with no launch, for N == 0. */
+int msmc_triple_loss_stream(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp,
+                            int N, int D, int H, int K, float margin, int mean, int chunk, msmc_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * E1/V3  fused element-wise / row-normalisation kernels of the FFT blocks and the quantiser glue (csrc/norm.hip).
  * Replace the stock-kernel chains behind

@@ -50,6 +50,8 @@ void msmc_conv_set_wgrad4_ablate(int mask);
 /* ---- observers (read-only: nothing here changes what a product call computes or launches) ---- */
 /* Symbol of the search kernel the calling thread's most recent msmc_vq_search launched (profiling aid). */
 const char* msmc_vq_last_kernel(void);
+/* Symbol of the kernel the calling thread's most recent triple-loss call launched, resident or streamed (profiling aid). */
+const char* msmc_loss_last_kernel(void);
 /* Per-launch profiling log (process-wide; bench.py's kernel table): while enabled, every kernel this library launches
  * -- from any thread: the backward pass runs on the autograd engine's -- is bracketed by a HIP event pair recorded on the launch's own stream and logged under the
  * symbol rocprofv3 prints for it (template arguments included where the launcher knows the instantiation, the template's

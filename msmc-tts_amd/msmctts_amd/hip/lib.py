@@ -120,6 +120,7 @@ _SIGNATURES.update({
     'msmc_mse_const_multi_fwd': (_i, [ctypes.POINTER(TensorTable), _f, _vp, _vp]),
     'msmc_mse_const_multi_bwd': (_i, [ctypes.POINTER(TensorTable), _f, _vp, _vp]),
     'msmc_triple_loss': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
+    'msmc_triple_loss_stream': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp]),
     'msmc_masked_mean_parts': (_i, [_i]),
     'msmc_masked_mean_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'msmc_masked_mean_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -207,6 +208,7 @@ _SIGNATURES.update({
 # the library for tools/ and tests/, not part of the product ABI
 _DEBUG_SIGNATURES = {
     'msmc_vq_last_kernel': (ctypes.c_char_p, []),
+    'msmc_loss_last_kernel': (ctypes.c_char_p, []),
     'msmc_conv_last_kernel': (ctypes.c_char_p, []),
     'msmc_conv_launch_count': (ctypes.c_long, []),
     'msmc_prof_enable': (None, [_i]),

@@ -183,16 +183,33 @@ def masked_mean(a, lengths, b=None):
     return _MaskedMean.apply(a.contiguous(), None if b is None else b.contiguous(), lengths.contiguous(), 0 if b is None else 1)
 
 
+LDS_LIMIT = 160 * 1024
+STREAM_DIMS = (16, 32, 64, 128, 256, 512)
+
+
+def triple_resident(d, K):
+    """the one-launch kernel with a head's whole codebook in LDS takes this head shape (msmc_triple_loss)"""
+    return d in (16, 32, 64, 128) and (K * d + K) * 4 <= LDS_LIMIT
+
+
+def triple_kernel_takes(d, K):
+    """one of the two triple-loss kernels takes this head shape: resident where it fits, streamed (csrc/triple_stream.inc) else"""
+    return d in STREAM_DIMS and K >= 1
+
+
 class _TripleLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, p, trg, embed_t, enorm, margin, mean):
+    def forward(ctx, p, trg, embed_t, enorm, margin, mean, chunk):
         N, D = p.shape
         H, K = enorm.shape
         lossh = torch.empty(N, H, dtype=torch.float32, device=p.device)
         gp = torch.empty(N, D, dtype=torch.float32, device=p.device)
-        lib.check(lib.get().msmc_triple_loss(lib.ptr(p, torch.float32), lib.ptr(trg, torch.int64), lib.ptr(embed_t, torch.float32),
-                                             lib.ptr(enorm, torch.float32), lib.ptr(lossh), lib.ptr(gp), N, D, H, K, float(margin),
-                                             int(mean), lib.stream(p)), 'msmc_triple_loss')
+        args = (lib.ptr(p, torch.float32), lib.ptr(trg, torch.int64), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
+                lib.ptr(lossh), lib.ptr(gp), N, D, H, K, float(margin), int(mean))
+        if chunk is None and triple_resident(D // H, K):
+            lib.check(lib.get().msmc_triple_loss(*args, lib.stream(p)), 'msmc_triple_loss')
+        else:
+            lib.check(lib.get().msmc_triple_loss_stream(*args, int(chunk or 0), lib.stream(p)), 'msmc_triple_loss_stream')
         ctx.save_for_backward(gp)
         ctx.heads = H
         return lossh
@@ -203,13 +220,16 @@ class _TripleLoss(torch.autograd.Function):
         N, D = gp.shape
         H = ctx.heads
         g = glossh.reshape(N, H, 1).to(gp.dtype)
-        return (gp.view(N, H, D // H) * g).view(N, D), None, None, None, None, None
+        return (gp.view(N, H, D // H) * g).view(N, D), None, None, None, None, None, None
 
 
-def triple_loss(p, trg, embed_t, enorm, reduction='sum', margin=1e-6):
+def triple_loss(p, trg, embed_t, enorm, reduction='sum', margin=1e-6, chunk=None):
     """per-(frame, head) triple loss of predictions ``p`` [N, D] against target indices ``trg`` [N, H] and the prepared codebook
-    (``hip/vq.py vq_prepare``: embed_t [H, K, d], enorm [H, K]) in one launch (msmc_triple_loss) -> [N, H]"""
-    return _TripleLoss.apply(p.contiguous().float(), trg.contiguous().long(), embed_t, enorm, float(margin), reduction == 'mean')
+    (``hip/vq.py vq_prepare``: embed_t [H, K, d], enorm [H, K]) in one launch -> [N, H].  ``chunk=None``: msmc_triple_loss where a
+    head's codebook fits LDS, else msmc_triple_loss_stream with the launcher's chunk; an int forces the streamed entry with that
+    chunk of codewords (0 = the launcher's choice)."""
+    return _TripleLoss.apply(p.contiguous().float(), trg.contiguous().long(), embed_t, enorm, float(margin), reduction == 'mean',
+                             chunk)
 
 
 def usable(*tensors):

@@ -75,11 +75,13 @@ class Quantize(nn.Module):
     def compute_triple_loss(self, prd_quant, trg_quant, reduction='mean', margin=1e-6, adaptive_margin=False):
         """hinge of (squared distance to the target codeword) against the squared distance to every codeword (reference
         modules.py:86-116, the 'masked version'): [B, T] per-frame loss.  On the GPU one launch per call (round 5); the stock
-        operator chain on the expanded distance matrix below serves reduction='none' and odd codeword widths."""
+        operator chain on the expanded distance matrix below serves reduction='none', odd codeword widths and, beyond the resident kernel's shapes, adaptive_margin."""
         B, T, D = prd_quant.shape
-        if (reduction in ('mean', 'sum') and hiploss.usable(prd_quant) and self.dim in (16, 32, 64, 128)
-                and (self.n_embed * self.dim + self.n_embed) * 4 <= 160 * 1024):       # (the head's codebook sits in LDS)
-            # one launch: all K distances, the hinge and its gradient per frame (csrc/losses.hip triple_loss_kernel)
+        if (reduction in ('mean', 'sum') and hiploss.usable(prd_quant)
+                and (hiploss.triple_resident(self.dim, self.n_embed)
+                     or (not adaptive_margin and hiploss.triple_kernel_takes(self.dim, self.n_embed)))):
+            # one launch: all K distances, the hinge and its gradient per frame (csrc/losses.hip triple_loss_kernel with the
+            # codebook in LDS; csrc/triple_stream.inc for d = 256 / 512 or a codebook beyond LDS)
             embed_t, enorm = hipvq.vq_prepare(self.embed.unsqueeze(0).contiguous(), frames=0)
             return hiploss.triple_loss(prd_quant.reshape(-1, D), trg_quant.reshape(-1, 1), embed_t, enorm, reduction,
                                        margin).reshape(B, T)
@@ -133,8 +135,9 @@ class MultiHeadQuantize(nn.Module):
     def compute_triple_loss(self, prd_quant, trg_quant, reduction='mean', margin=1e-6, adaptive_margin=False):
         """mean over heads of the per-head triple loss (reference modules.py:152-168); trg_quant [B, T, H] indices"""
         d = self.dim // self.n_head
-        if (reduction in ('mean', 'sum') and hiploss.usable(prd_quant) and d in (16, 32, 64, 128)
-                and (self.n_embed * d + self.n_embed) * 4 <= 160 * 1024 and trg_quant.shape[-1] == self.n_head):
+        if (reduction in ('mean', 'sum') and hiploss.usable(prd_quant) and trg_quant.shape[-1] == self.n_head
+                and (hiploss.triple_resident(d, self.n_embed)
+                     or (not adaptive_margin and hiploss.triple_kernel_takes(d, self.n_embed)))):
             # all heads in one launch on the packed codebook; the mean over heads as the reference's sum(losses) / len(losses)
             B, T, D = prd_quant.shape
             embed, _, _ = self._packed()

@@ -1,0 +1,65 @@
+"""CPU: the streamed triple loss (csrc/triple_stream.inc) on the kernel interpreter, through the C entries, hip/losses.py, the
+quantiser modules and one PredictorTrainer step (cases and references: tests/_triplestreamcases.py; the same on the GPU, with the
+hipGraph-replayed step: tests/test_gpu_triple_stream.py)."""
+import os
+import subprocess
+
+import pytest
+
+import _triplestreamcases as cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU = os.path.join(ROOT, 'tests', 'emu', 'libmsmc_emu.so')
+DEV = 'cpu'
+
+
+@pytest.fixture(scope='module', autouse=True)
+def emulator():
+    subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'tests', 'emu')])
+    from msmctts_amd.hip import lib
+    saved = (lib._lib, lib._host_pointers_ok)
+    lib.use_library_for_tests(EMU)
+    assert lib.backend() == 'emu'
+    yield
+    lib._lib, lib._host_pointers_ok = saved
+
+
+@pytest.mark.parametrize('s,n', cases.SAME_PARAMS, ids=cases.SAME_IDS)
+def test_forced_chunks_give_the_bits_of_the_resident_kernel(s, n):
+    cases.check_same_bits_as_resident(DEV, s, n)
+
+
+@pytest.mark.parametrize('s,n', cases.LARGE_PARAMS, ids=cases.LARGE_IDS)
+def test_large_shapes_do_not_depend_on_the_chunk(s, n):
+    cases.check_chunk_invariance(DEV, s, n)
+
+
+@pytest.mark.parametrize('s,n', cases.LARGE_PARAMS, ids=cases.LARGE_IDS)
+def test_large_shapes_are_exact_on_an_integer_lattice(s, n):
+    cases.check_lattice(DEV, s, n)
+
+
+@pytest.mark.parametrize('s,n', cases.LARGE_PARAMS, ids=cases.LARGE_IDS)
+def test_large_shapes_match_float64_within_the_derived_budget(s, n):
+    cases.check_real_values(DEV, s, n)
+
+
+@pytest.mark.parametrize('m', range(len(cases.MODULES)), ids=cases.MODULE_IDS)
+def test_quantiser_modules_take_the_streamed_kernel(m):
+    cases.check_module(DEV, m)
+
+
+def test_predictor_step_against_a_large_codebook_matches_the_oracle():
+    cases.check_predictor_step(DEV)
+
+
+def test_refused_arguments_and_the_empty_input():
+    cases.check_refusals(DEV)
+
+
+def test_wrapper_routes_between_the_two_entries():
+    cases.check_wrapper_routes(DEV)
+
+
+def test_the_symbols_are_exported_and_bound():
+    cases.check_feature_present()
