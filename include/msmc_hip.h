@@ -50,7 +50,8 @@ int msmc_stream_destroy(msmc_stream stream);
  *   reference msmctts/networks/vqgantts/modules.py:24-67 and :137-151.
  * ------------------------------------------------------------------------------------------- */
 
-/* embed [H][d][K] -> embed_t [H][K][d], enorm[h][k] = sum_j embed[h][j][k]^2   (modules.py:29). */
+/* embed [H][d][K] -> embed_t [H][K][d], enorm[h][k] = sum_j embed[h][j][k]^2   (modules.py:29).  d <= 2559 (a tile of 16
+ * transposed rows must fit LDS; MSMC_E_SHAPE beyond). */
 int msmc_vq_prepare(const float* embed, float* embed_t, float* enorm, int H, int d, int K,
                     msmc_stream stream);
 
@@ -72,6 +73,15 @@ int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, flo
  * multiple of 16 or does not fit, N * D * 4 >= 2^32; 0 at once for N == 0.  quant may alias x. */
 int msmc_vq_search_stream(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
                           int64_t* ind, int N, int D, int H, int K, int chunk, msmc_stream stream);
+
+/* Nearest-centroid search of ONE wide head with any number of centroids (msmc-tts_amd/csrc/vq_wide.inc): the k-means unit
+ * codebooks of KMeansVQGANEmb (d = 768 / 1024, K = 100 .. 2000), which msmc_vq_search refuses.  Operands as msmc_vq_search
+ * with H = 1 (embed_t [K][d] / enorm [K] from msmc_vq_prepare, diff [N][d]); same distance expression and first-minimum
+ * tie rule, computed as a GEMM with an arg-min epilogue: frame tiles x centroid tiles, the d axis in double-buffered
+ * 32-channel LDS slices, fp32 MFMA.  Takes d % 16 == 0, 16 <= d <= 2048, K >= 1, N >= 0 with N * d * 4 < 2^32
+ * (MSMC_E_SHAPE otherwise, nothing launched); 0 at once for N == 0.  quant may alias x. */
+int msmc_vq_search_wide(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
+                        int64_t* ind, int N, int d, int K, msmc_stream stream);
 
 /* The same search -- identical indices, quant and diff, bit for bit -- under the HBM roof for K >= 64
  * (msmc-tts_amd/csrc/vq_shortlist.inc): all K distances approximately on the bf16 matrix cores (two-piece bf16 splits of

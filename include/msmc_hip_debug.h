@@ -22,6 +22,9 @@ void msmc_vq_set_shortlist_ablate(int mask);
 /* Perf-experiment switch: 0 selects the LDS-tile search kernel for every shape; default 1. */
 void msmc_vq_set_variant(int v);
 
+/* Tests / sweeps: waves that share a 16-frame tile in msmc_vq_search_wide, 1 / 2 / 4 (0, the default: chosen from N). */
+void msmc_vq_wide_set_split(int wc);
+
 /* Tests / sweeps: workgroups of the persistent grid of msmc_conv_gather variant 32 (0 = one or two per CU). */
 void msmc_conv_set_gather4_grid(int n);
 /* 1: the variant-32 members of msmc_conv_gather_group share ONE persistent grid (interpreter-tested, not yet timed on the

@@ -12,6 +12,7 @@
 // gather, straight-through value and squared error are formed in LDS in place and written back
 // with full-row stores.  Algorithmic HBM bytes per frame: 4D (x) + 4D (quant) + 8H (ind) + 4D/H (diff).
 //
+// One wide head (d up to 2048, any K: k-means unit codebooks) takes the GEMM-shaped kernel of vq_wide.inc (msmc_vq_search_wide).
 // Codebooks too large to stay resident (one head beyond 160 KiB of LDS) take the streamed kernel of vq_stream.inc: same
 // distances, same summation order, same bits, the codebook passing through LDS in double-buffered chunks.
 //
@@ -39,7 +40,9 @@ extern "C" const char* msmc_vq_last_kernel(void) { return msmc_vq_last; }
 // LDS tile and leaves with j fastest (whole rows of embed_t); the squared norms are summed by one work-item per codeword in
 // the order j = 0 .. d-1 (the order of the previous one-work-item-per-codeword form: 33 us for 256 KB -- every store
 // instruction of a wave touched 64 cache lines).
-#define VQP_K 32
+// VQP_K = 32 codewords per workgroup; beyond d = 1279 the tile of 32 rows exceeds LDS and 16 are taken (the wide search's
+// d up to 2048): the same values, every norm summed in the same order.
+template <int VQP_K>
 __global__ __launch_bounds__(256) void vq_prepare_kernel(const float* __restrict__ embed, float* __restrict__ embed_t,
                                                         float* __restrict__ enorm, int d, int K) {
     MSMC_DYN_LDS(smem);
@@ -455,6 +458,7 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
 
 #include "vq_shortlist.inc"
 #include "vq_stream.inc"
+#include "vq_wide.inc"
 
 typedef void (*vq_search_reg_fn)(const float*, const float*, const float*, float*, float*, int64_t*, int, int, int, int,
                                  int);
@@ -644,11 +648,15 @@ extern "C" {
 
 int msmc_vq_prepare(const float* embed, float* embed_t, float* enorm, int H, int d, int K, msmc_stream stream) {
     if (H <= 0 || d <= 0 || K <= 0) return MSMC_E_SHAPE;
-    dim3 grid((K + VQP_K - 1) / VQP_K, H);
-    const size_t lds = (size_t)VQP_K * (d + 1) * sizeof(float);
-    int rc = msmc_allow_lds((const void*)vq_prepare_kernel, (int)lds);
+    const int kt = (size_t)32 * (d + 1) * sizeof(float) <= VQ_LDS_LIMIT ? 32 : 16;
+    const size_t lds = (size_t)kt * (d + 1) * sizeof(float);
+    if (lds > VQ_LDS_LIMIT) return MSMC_E_SHAPE;
+    dim3 grid((K + kt - 1) / kt, H);
+    void (*fn)(const float*, float*, float*, int, int) = kt == 32 ? vq_prepare_kernel<32> : vq_prepare_kernel<16>;
+    int rc = msmc_allow_lds((const void*)fn, (int)lds);
     if (rc) return rc;
-    MSMC_LAUNCH(vq_prepare_kernel, grid, dim3(256), lds, (msmc_stream_t)stream, embed, embed_t, enorm, d, K);
+    MSMC_LAUNCH(fn, grid, dim3(256), lds, (msmc_stream_t)stream, embed, embed_t, enorm, d, K);
+    msmc_prof_name("vq_prepare_kernel");
     return msmc_check_launch();
 }
 
@@ -731,6 +739,12 @@ int msmc_vq_search_stream(const float* x, const float* embed_t, const float* eno
     if (chunk < 0 || chunk % 16) return MSMC_E_SHAPE;
     if (N == 0) return 0;
     return vq_stream_launch(x, embed_t, enorm, quant, diff, ind, N, D, H, K, chunk, d % 16 == 0 && vq_use_reg_kernel, stream);
+}
+
+// ---- one wide head, any K (vq_wide.inc) --------------------------------------------------------------------------------
+int msmc_vq_search_wide(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff, int64_t* ind,
+                        int N, int d, int K, msmc_stream stream) {
+    return vq_wide_launch(x, embed_t, enorm, quant, diff, ind, N, d, K, stream);
 }
 
 // ---- shortlist search (vq_shortlist.inc) ----------------------------------------------------------------------------

@@ -28,6 +28,7 @@ _SIGNATURES = {
     'msmc_vq_prepare': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_vq_search': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'msmc_vq_search_stream': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'msmc_vq_search_wide': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_vq_shortlist_bytes': (_sz, [_i, _i, _i]),
     'msmc_vq_prepare_shortlist': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_vq_search_shortlist': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -216,6 +217,7 @@ _DEBUG_SIGNATURES = {
     'msmc_prof_read': (_i, [_i, ctypes.c_char_p, _i, ctypes.POINTER(ctypes.c_float)]),
     'msmc_vq_set_shortlist_ablate': (None, [_i]),
     'msmc_vq_set_variant': (None, [_i]),
+    'msmc_vq_wide_set_split': (None, [_i]),
     'msmc_conv_set_grouping': (None, [_i]),
     'msmc_conv_set_pipeline': (None, [_i]),
     'msmc_conv_set_wgrad_split': (None, [_i]),

@@ -56,9 +56,22 @@ def _f32_frames(x):
     return x.detach().contiguous().float()
 
 
+E_SHAPE = -2                # MSMC_E_SHAPE of include/msmc_hip.h
+
+
+def wide_takes(H, d, K):
+    """the shapes ``msmc_vq_search_wide`` takes: one head, d % 16 == 0, 16 <= d <= 2048, any K >= 1"""
+    return H == 1 and d % 16 == 0 and 16 <= d <= 2048 and K >= 1
+
+
+def _search_wide(L, xc, embed_t, enorm, quant, diff, ind, N, d, K):
+    return L.msmc_vq_search_wide(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32), lib.ptr(quant),
+                                 lib.ptr(diff), lib.ptr(ind), N, d, K, lib.stream(xc))
+
+
 class _VQSearch(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, embed_t, enorm, image=None, force_shortlist=False, stream_chunk=None):
+    def forward(ctx, x, embed_t, enorm, image=None, force_shortlist=False, stream_chunk=None, wide=False):
         H, K, d = embed_t.shape
         D = H * d
         assert x.shape[-1] == D, (x.shape, embed_t.shape)
@@ -69,7 +82,11 @@ class _VQSearch(torch.autograd.Function):
         diff = torch.empty(xc.shape[:-1] + (d,), dtype=torch.float32, device=x.device)
         ind = torch.empty(xc.shape[:-1] + (H,), dtype=torch.int64, device=x.device)
         L = lib.get()
-        if stream_chunk is not None:
+        if wide:
+            if H != 1:
+                raise RuntimeError('msmc_vq_search_wide takes one head (got %d)' % H)
+            lib.check(_search_wide(L, xc, embed_t, enorm, quant, diff, ind, N, d, K), 'msmc_vq_search_wide')
+        elif stream_chunk is not None:
             lib.check(L.msmc_vq_search_stream(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
                                               lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, int(stream_chunk),
                                               lib.stream(xc)), 'msmc_vq_search_stream')
@@ -79,9 +96,14 @@ class _VQSearch(torch.autograd.Function):
                                                  lib.ptr(SLOW_COUNT, torch.int64), N, D, H, K, lib.stream(xc)),
                       'msmc_vq_search_shortlist')
         else:
-            lib.check(L.msmc_vq_search(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
-                                       lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, lib.stream(xc)),
-                      'msmc_vq_search')
+            rc = L.msmc_vq_search(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
+                                  lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, lib.stream(xc))
+            if rc == E_SHAPE and wide_takes(H, d, K):
+                # a single head msmc_vq_search refuses (it launched nothing): K % 16 != 0, or a d beyond what the streamed
+                # launcher fits -- the GEMM-shaped kernel of csrc/vq_wide.inc
+                lib.check(_search_wide(L, xc, embed_t, enorm, quant, diff, ind, N, d, K), 'msmc_vq_search_wide')
+            else:
+                lib.check(rc, 'msmc_vq_search')
         ctx.save_for_backward(xc, quant)
         ctx.heads = H
         ctx.in_dtype = x.dtype
@@ -95,7 +117,7 @@ class _VQSearch(torch.autograd.Function):
         D = xc.shape[-1]
         N = xc.numel() // D
         if g_quant is None and g_diff is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         if g_quant is None:
             g_quant = torch.zeros_like(xc)
         g_quant = g_quant.contiguous().float()
@@ -104,16 +126,20 @@ class _VQSearch(torch.autograd.Function):
         L = lib.get()
         lib.check(L.msmc_vq_backward(lib.ptr(g_quant), lib.ptr(g_diff), lib.ptr(xc), lib.ptr(quant), lib.ptr(gx),
                                      N, D, ctx.heads, lib.stream(xc)), 'msmc_vq_backward')
-        return gx.to(ctx.in_dtype), None, None, None, None, None
+        return gx.to(ctx.in_dtype), None, None, None, None, None, None
 
 
-def vq_search(x, embed_t, enorm, shortlist=None, stream_chunk=None):
+def vq_search(x, embed_t, enorm, shortlist=None, stream_chunk=None, wide=False):
     """x [..., D] -> (quant [..., D] straight-through, diff [..., d], ind [..., H] int64).  ``shortlist``: None = the
     product's choice (the shortlist kernel where ``vq_prepare`` attached an image and the problem is large enough),
     True = the shortlist kernel whatever the size (it must have an image), False = the exact kernel.  ``stream_chunk``:
     None = the product's choice through ``msmc_vq_search`` (resident codebook where one head fits LDS, the streamed kernel of
     csrc/vq_stream.inc where it does not); an int = ``msmc_vq_search_stream`` with that chunk of codewords (0 = the
-    launcher's choice) whatever the shape -- same bits, for tests and tools."""
+    launcher's choice) whatever the shape -- same bits, for tests and tools.  A single head whose shape ``msmc_vq_search``
+    refuses (K % 16 != 0, d = 1024) runs ``msmc_vq_search_wide`` (csrc/vq_wide.inc) where that kernel takes it; ``wide=True``
+    = that kernel whatever the shape (tools: its summation order differs from the resident kernels', so near-ties may not)."""
+    if wide:
+        return _VQSearch.apply(x, embed_t, enorm, None, False, None, True)
     if stream_chunk is not None:
         return _VQSearch.apply(x, embed_t, enorm, None, False, int(stream_chunk))
     image = getattr(embed_t, 'shortlist_image', None) if (SHORTLIST if shortlist is None else shortlist) else None

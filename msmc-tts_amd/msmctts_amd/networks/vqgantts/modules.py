@@ -7,6 +7,11 @@ signatures, but one forward is three HIP launches for *all* heads (csrc/vq.hip):
 transpose + norms, fused search/gather/straight-through/squared-error, and -- in training with
 ``update`` -- the deterministic EMA update.  The per-head buffers are views into head-packed
 tensors so the kernels see [H][d][K] while ``state_dict`` keeps the reference keys.
+
+A single-head ``Quantize`` whose shape ``msmc_vq_search`` refuses (``n_embed % 16 != 0``, or an ``embed_dim`` beyond what the
+streamed launcher fits: the k-means unit codebooks, d = 1024) searches on ``msmc_vq_search_wide`` (csrc/vq_wide.inc; hip/vq.py
+routes it) where that kernel takes the shape; the backward is ``msmc_vq_backward`` either way.  The EMA kernels keep their
+``d <= 512`` limit: ``forward(update=True)`` in training beyond it raises.
 """
 import torch
 import torch.nn as nn

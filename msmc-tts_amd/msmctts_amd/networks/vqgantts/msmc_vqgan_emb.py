@@ -14,7 +14,29 @@ The speaker / style reference encoder (``global_encoder_config._name == 'ECAPA_T
 embedding of ``ref`` (training: of ``mel`` when no ``ref`` is given) is added to every frame of the frame decoder's input
 (:195-199, :254-258).  Sizes its kernels do not take (``n_model_size % 64``, ``mel_dim % 8``) are refused at construction with
 ``NotImplementedError``; an unknown encoder name raises ``ValueError`` as in the reference.
+
+``KMeansQuantizer`` / ``KMeansVQGANEmb`` (reference :294-469) are the discrete-unit baseline: the embedding frames themselves are
+snapped to the centroids of a frozen, offline k-means model (one head of emb_dim channels, any number of centroids: the search
+runs ``msmc_vq_search_wide``, csrc/vq_wide.inc, where the other search kernels refuse the shape), then pass through ``in_linear``,
+the optional global encoder and frame decoder and the vocoder.  Same class names, constructor keywords, ``state_dict`` keys
+(``quantizer.quantizer.0.{embed,cluster_size,embed_avg}``, ``in_linear``, ``decoder``, ``frame_decoder``, ``global_encoder``,
+``mel_predictor``) and output-dictionary keys (``encoder_indices``, ``mel_outputs``, ``decoder_outputs``); ``forward`` takes the
+``window`` / ``window_frames`` forms of ``MSMCVQGANEmb.forward``.  ``quantizer_path`` is a pickle holding an object with
+``cluster_centers_`` [K, d] as in the reference (unpickling a scikit-learn model needs scikit-learn installed; nothing here
+imports it) or, in addition, a ``.npy`` file of shape [K, d].  Deviations from the reference:
+
+* the reference assigns ``embed`` from the file at every forward (:316), so a checkpoint's ``embed`` never counts.  Here the
+  centroids are copied into the buffer at construction and again after every ``load_state_dict``: the same observable result;
+* the reference's training-mode ``analysis`` unpacks the quantiser's dictionary with ``zip(*...)`` (:429) and cannot work; here it
+  raises ``NotImplementedError`` naming that line;
+* ``synthesis`` hands the quantiser a ``zip`` the reference's quantiser has consumed by the time it lists the lengths (:329, :440),
+  so its ``quantizer_lengths`` come out empty; nothing reads them there, and here they are the lengths given;
+* sizes the downstream kernels refuse (``n_model_size % 64``, ``mel_dim % 8`` with a global encoder) raise at construction, as
+  for ``MSMCVQGANEmb``.
 """
+import pickle
+
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -23,6 +45,7 @@ from ...hip import norm as hipnorm
 from ...hip import window as hipwindow
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
+from .modules import Quantize
 from .msmc_vqgan import MultiStageQuantizer, PriorPredictor, _fft_pos
 from .tdnn import ECAPA_TDNN
 
@@ -179,3 +202,99 @@ class MSMCVQGANEmb(nn.Module):
                    'target_indices': quantizer_states['quantizer_indices'][i],
                    'target_lengths': quantizer_lengths[i]} for i in range(len(quantizer_outputs))]
         return self.quantizer.compute_embedding_loss(states, methods, loss_weights)
+
+
+def _load_centroids(path):
+    """[K, d] float32 from a ``.npy`` file or a pickled object with ``cluster_centers_`` (reference :297-300)"""
+    if str(path).endswith('.npy'):
+        centers = np.load(path, allow_pickle=False)
+    else:
+        with open(path, 'rb') as fin:
+            centers = pickle.load(fin).cluster_centers_
+    centers = torch.as_tensor(np.asarray(centers), dtype=torch.float32)
+    if centers.dim() != 2 or centers.shape[0] < 1 or centers.shape[1] < 1:
+        raise ValueError('%s: expected centroids of shape [K, d], got %s' % (path, tuple(centers.shape)))
+    return centers
+
+
+class KMeansQuantizer(nn.Module):
+    """one frozen ``Quantize`` over the centroids of an offline k-means model (reference :294-336); only ever searched with
+    ``update=False``"""
+
+    def __init__(self, model_path):
+        super().__init__()
+        codewords = _load_centroids(model_path).t().contiguous()                 # [d, K], the layout of ``Quantize.embed``
+        self.register_buffer('codewords', codewords, persistent=False)           # (not a ``state_dict`` key, as in the reference)
+        self.quantizer = nn.ModuleList([Quantize(codewords.shape[0], codewords.shape[1])])
+        self._restore()
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._restore())
+
+    def _restore(self):
+        with torch.no_grad():
+            self.quantizer[0].embed.copy_(self.codewords)
+
+    def forward(self, encoder_states, from_encoder=True):
+        encoder_states = list(encoder_states)
+        states = [self.quantizer[i](embedding, length, update=False) for i, (embedding, length) in enumerate(encoder_states)]
+        outputs, diffs, indices = zip(*states)
+        return {'residual_output': None, 'quantizer_outputs': outputs, 'quantizer_diffs': diffs, 'quantizer_indices': indices,
+                'quantizer_lengths': [length for _, length in encoder_states], 'predictor_diffs': None}
+
+
+class KMeansVQGANEmb(nn.Module):
+    def __init__(self, emb_dim, n_model_size, quantizer_path, global_encoder_config=None, frame_decoder_config=None,
+                 decoder_config=None, pred_mel=False, mel_dim=None):
+        super().__init__()
+        if global_encoder_config is not None:
+            name = (global_encoder_config.get('_name') if isinstance(global_encoder_config, dict)
+                    else getattr(global_encoder_config, '_name', None))
+            if name != 'ECAPA_TDNN':
+                raise ValueError('Wrong global encoder: {}'.format(name))
+            self.global_encoder = ECAPA_TDNN(in_channels=mel_dim, embd_dim=n_model_size, channels=n_model_size)
+        self.quantizer = KMeansQuantizer(quantizer_path)
+        self.in_linear = nn.Linear(emb_dim, n_model_size)
+        decoder_config = dict(decoder_config)
+        decoder_config['num_mels'] = n_model_size
+        self.decoder = HifiGANGenerator(**decoder_config)
+        if frame_decoder_config is not None:
+            self.frame_decoder = FFTBlocks(d_model=n_model_size, name='frame_decoder', **frame_decoder_config)
+        if pred_mel:
+            self.mel_predictor = nn.Linear(n_model_size, mel_dim if mel_dim is not None else emb_dim)
+
+    _decode_frames = MSMCVQGANEmb._decode_frames
+    _window = MSMCVQGANEmb._window
+
+    def forward(self, emb, emb_length, pitch=None, energy=None, mel=None, ref=None, window='full', window_frames=None):
+        """``window`` / ``window_frames`` as ``MSMCVQGANEmb.forward``; ``pitch`` / ``energy`` are accepted and unused, as in the
+        reference (:380-383)"""
+        if self.training:
+            hipnorm.advance_seed(emb.device)
+        qs = self.quantizer([(emb, emb_length)])
+        out = {'encoder_indices': qs['quantizer_indices']}
+        dec_in = self._decode_frames(self.in_linear(qs['quantizer_outputs'][-1]), emb_length, mel if ref is None else ref)
+        if hasattr(self, 'mel_predictor'):
+            out['mel_outputs'] = self.mel_predictor(dec_in)
+        if window is not None:
+            dec_in = self._window(dec_in, window, window_frames)
+            out['decoder_outputs'] = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
+        return out
+
+    def analysis(self, emb, emb_length):
+        if self.training:
+            raise NotImplementedError('KMeansVQGANEmb.analysis in training mode: the reference unpacks the quantiser\'s dictionary '
+                                      'with zip(*...) there (msmc_vqgan_emb.py:429) and cannot run; call it in eval mode')
+        return self.quantizer([(emb, emb_length)])
+
+    def synthesis(self, quantizer_outputs, quantizer_lengths, ref=None):
+        """the sequences are quantised again (reference :440): centroid rows map to themselves"""
+        qs = self.quantizer(zip(quantizer_outputs, quantizer_lengths))
+        if hasattr(self, 'global_encoder'):
+            assert ref is not None
+        dec_in = self._decode_frames(self.in_linear(qs['quantizer_outputs'][-1]), quantizer_lengths[-1], ref)
+        wav = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
+        if self.training:
+            out = {'decoder_outputs': wav}
+            if hasattr(self, 'mel_predictor'):
+                out['mel_outputs'] = self.mel_predictor(dec_in)
+            return out
+        return wav

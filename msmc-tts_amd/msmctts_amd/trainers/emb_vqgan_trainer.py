@@ -15,6 +15,12 @@ What differs from ``VQGANTrainer``:
 Losses, their weights, the loss-dictionary keys, the discriminator and generator steps, clipping and the optimizer order are
 the parent's (the fused loss kernels, the single D([fake; real]) pass, the front-end reuse, the side branches).
 
+A task whose autoencoder is ``KMeansVQGANEmb`` trains here as well, in all three phases.  That model returns
+``encoder_indices`` but no ``encoder_diffs`` (its codebook is frozen and its input is data: a VQ term could train nothing), on
+which the reference's step fails with a ``KeyError``; here a model output without ``encoder_diffs`` takes no VQ term and the
+loss dictionary carries no VQ keys (one guarded branch in ``VQGANTrainer._segment_a``).  Outputs that have ``encoder_diffs``
+behave as before.
+
 ``stft_loss_supervised_step``: the reference reads ``self.stft_loss_supervised_step`` (:123) but no constructor sets it, and
 its own YAML passes it as a trainer kwarg (line 94) that its constructor would reject; here it is an ordinary kwarg.
 

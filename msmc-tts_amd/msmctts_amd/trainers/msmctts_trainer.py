@@ -186,9 +186,12 @@ class VQGANTrainer(BaseTrainer):
         disc = getattr(self.model, 'discriminator', None)
         with self._amp():
             out = self._autoencode(st)
-        vq = self.vq_criterion(out)
-        losses.update(vq)
-        g_loss = vq['vq_loss']
+        if 'encoder_diffs' in out:
+            vq = self.vq_criterion(out)
+            losses.update(vq)
+            g_loss = vq['vq_loss']
+        else:                               # a frozen codebook over data (KMeansVQGANEmb): no VQ term, no VQ keys
+            g_loss = None
         if 'mel_outputs' in out:
             if _fused_masked(out['mel_outputs'], mel_length) and mel.dtype == torch.float32 and mel.is_contiguous():
                 # masked mean of (mel - mel_outputs)^2, the prediction read in its own dtype (no cast pass)
@@ -201,8 +204,13 @@ class VQGANTrainer(BaseTrainer):
             g_terms, g_weights = [g_loss, ml], [1.0, self.lambda_frame]
         else:
             g_terms, g_weights = [g_loss], [1.0]
+        if g_loss is None:
+            g_terms, g_weights = g_terms[1:], g_weights[1:]
         if not self._spectral_on(st):
-            st.g_loss = hiploss.weighted_sum(g_terms, g_weights) if len(g_terms) > 1 else g_loss
+            if not g_terms:
+                raise RuntimeError('a step with no loss term: the model returns neither encoder_diffs nor mel_outputs, and the '
+                                   'vocoder does not run in this phase')
+            st.g_loss = hiploss.weighted_sum(g_terms, g_weights) if (len(g_terms) > 1 or g_weights[0] != 1.0) else g_terms[0]
             return
         st.predict = predict = out['decoder_outputs'].squeeze(-1).float()
         target = st.target
