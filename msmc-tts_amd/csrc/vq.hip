@@ -5,16 +5,15 @@
 //
 // msmc_vq_search: one persistent launch for all heads.  Each wave owns 16-frame tiles whose rows
 // are streamed HBM -> registers (prefetch, one tile ahead) -> LDS with full-row coalesced
-// loads; the transposed codebook of the resident heads sits in LDS; x.e products run on the
-// f32 matrix cores (v_mfma_f32_16x16x4_f32: exact fp32, k-ordered fmaf chain, two independent
-// accumulators per wave to cover the 40-cycle dependent latency); the arg-min is a per-lane
-// running minimum over the accumulator fragment followed by a two-step wave xor-reduce; the
-// gather, straight-through value and squared error are formed in LDS in place and written back
-// with full-row stores.  Algorithmic HBM bytes per frame: 4D (x) + 4D (quant) + 8H (ind) + 4D/H (diff).
+// loads; the transposed codebook of the resident heads sits in LDS; the x.e products (f32 matrix
+// cores), the per-lane running minimum, the merge of the four lane groups of a frame and the
+// straight-through value / squared error are the pieces of vq_common.inc; quant and diff are
+// formed in LDS in place and written back with full-row stores.
+// Algorithmic HBM bytes per frame: 4D (x) + 4D (quant) + 8H (ind) + 4D/H (diff).
 //
 // One wide head (d up to 2048, any K: k-means unit codebooks) takes the GEMM-shaped kernel of vq_wide.inc (msmc_vq_search_wide).
-// Codebooks too large to stay resident (one head beyond 160 KiB of LDS) take the streamed kernel of vq_stream.inc: same
-// distances, same summation order, same bits, the codebook passing through LDS in double-buffered chunks.
+// Codebooks too large to stay resident (one head beyond 160 KiB of LDS) take the streamed kernel of vq_stream.inc: the same
+// pieces of vq_common.inc, hence the same bits, the codebook passing through LDS in double-buffered chunks.
 //
 // msmc_vq_ema_update: deterministic two-stage reduction (per-tile counting sort of the indices in
 // LDS, ordered per-codeword sums, fixed-order reduction over tiles) then the EMA / Laplace
@@ -32,6 +31,27 @@ extern "C" void msmc_vq_set_variant(int v) { vq_use_reg_kernel = v; }
 // symbol of the search kernel the calling thread's most recent msmc_vq_search launched (bench.py's micro-benchmark table)
 static thread_local const char* msmc_vq_last = "";
 extern "C" const char* msmc_vq_last_kernel(void) { return msmc_vq_last; }
+
+#include "vq_common.inc"
+
+// ---- launcher pieces shared by the exact searches ---------------------------------------------------------------------
+// what msmc_vq_search and msmc_vq_search_stream accept: whole heads, d % 4 == 0, whole 16-codeword tiles
+static inline int vq_check_search_shape(int N, int D, int H, int K) {
+    if (N < 0 || H <= 0 || D <= 0 || D % H) return MSMC_E_SHAPE;
+    if ((D / H) % 4 || K % 16 || K <= 0) return MSMC_E_SHAPE;
+    return 0;
+}
+// the instantiation of a kernel family templated on d / 16 (register form); nullptr where the family has none.  Launchers
+// only (msmc_vq_search, vq_stream_launch); undefined again behind them.
+#define VQ_BY_D4H(kernel, d4h) \
+    ((d4h) == 1 ? kernel<1> : (d4h) == 2 ? kernel<2> : (d4h) == 4 ? kernel<4> : (d4h) == 8 ? kernel<8> : (d4h) == 16 ? kernel<16> : nullptr)
+// persistent grid: a workgroup of nw waves takes nw tiles of `tile` frames per iteration; at most wgs workgroups.  `tile` is
+// VQ_TILE for the exact kernels; the shortlist kernel's waves take two 16-frame column tiles each and pass 32.
+static inline int vq_grid(int N, int nw, int wgs, int tile = VQ_TILE) {
+    const int numTiles = (N + tile - 1) / tile;
+    const int numIters = (numTiles + nw - 1) / nw;
+    return numIters < wgs ? numIters : wgs;
+}
 
 // ------------------------------------------------------------------------------------------------
 // prepare: embed [H][d][K] -> embed_t [H][K][d], enorm [H][K]
@@ -113,20 +133,8 @@ __global__ __launch_bounds__(256) void vq_search_kernel(const float* __restrict_
     const int numTiles = (N + VQ_TILE - 1) / VQ_TILE;
     const int numIters = (numTiles + nw - 1) / nw;
 
-    // ---- stage the codebook of heads [h0, h0+cnt) : rows of d floats -> stride ES
-    auto stage_group = [&](int h0, int cnt) {
-        const int rows = cnt * K;
-        const int dv = d >> 2;
-        const f32x4* src = (const f32x4*)(embed_t + (size_t)h0 * K * d);
-        for (int e = threadIdx.x; e < rows * dv; e += blockDim.x) {
-            int r = e / dv, c4 = e - r * dv;
-            *(f32x4*)(cb + r * ES + c4 * 4) = src[e];
-        }
-        for (int e = threadIdx.x; e < rows; e += blockDim.x) en[e] = enorm[(size_t)h0 * K + e];
-    };
-
     if (ngroups == 1) {
-        stage_group(0, H);
+        vq_stage_heads(cb, en, embed_t, enorm, 0, H, K, d, ES);
         __syncthreads();
     }
 
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(256) void vq_search_kernel(const float* __restrict_
             const int cnt = (H - h0 < hpg) ? (H - h0) : hpg;
             if (ngroups > 1) {
                 __syncthreads();
-                stage_group(h0, cnt);
+                vq_stage_heads(cb, en, embed_t, enorm, h0, cnt, K, d, ES);
                 __syncthreads();
             }
             if (!active) continue;
@@ -177,15 +185,7 @@ __global__ __launch_bounds__(256) void vq_search_kernel(const float* __restrict_
                 const float* cbh = cb + hl * K * ES;
                 const float* enh = en + hl * K;
                 float* xr = xt + f * XS + h * d;
-                // |x|^2 : four interleaved partial sums, combined across the 4 lane groups
-                float xx = 0.f;
-                for (int j = g; j < d; j += 4) {
-                    float v = xr[j];
-                    float sq = v * v;
-                    xx = xx + sq;
-                }
-                xx = xx + wave_xor(xx, 16);
-                xx = xx + wave_xor(xx, 32);
+                const float xx = vq_sumsq_lds(xr, d, g);
 
                 float best = __builtin_inff();
                 int bi = 0;
@@ -194,61 +194,25 @@ __global__ __launch_bounds__(256) void vq_search_kernel(const float* __restrict_
                 for (; ct + 2 <= ntile; ct += 2) {
                     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
                     const float* a0 = cbh + (ct * 16 + f) * ES + g;
-                    const float* a1 = a0 + 16 * ES;
-                    const float* b = xr + g;
-                    for (int s = 0; s < d; s += 4) {
-                        float bv = b[s];
-                        acc0 = mfma_f32_16x16x4(a0[s], bv, acc0);
-                        acc1 = mfma_f32_16x16x4(a1[s], bv, acc1);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 4 * g + r;
-                        float t2 = 2.f * acc0[r];
-                        float dist = (xx - t2) + enh[code];
-                        if (dist < best) { best = dist; bi = code; }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 16 + 4 * g + r;
-                        float t2 = 2.f * acc1[r];
-                        float dist = (xx - t2) + enh[code];
-                        if (dist < best) { best = dist; bi = code; }
-                    }
+                    vq_dot_lds2(a0, a0 + 16 * ES, xr + g, d, acc0, acc1);
+                    const int code0 = ct * 16 + 4 * g;
+                    vq_take_min(acc0, xx, enh + code0, code0, best, bi);
+                    vq_take_min(acc1, xx, enh + code0 + 16, code0 + 16, best, bi);
                 }
                 if (ct < ntile) {
                     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f};
-                    const float* a0 = cbh + (ct * 16 + f) * ES + g;
-                    const float* b = xr + g;
-                    for (int s = 0; s < d; s += 4) acc0 = mfma_f32_16x16x4(a0[s], b[s], acc0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 4 * g + r;
-                        float t2 = 2.f * acc0[r];
-                        float dist = (xx - t2) + enh[code];
-                        if (dist < best) { best = dist; bi = code; }
-                    }
+                    vq_dot_lds(cbh + (ct * 16 + f) * ES + g, xr + g, d, acc0);
+                    const int code0 = ct * 16 + 4 * g;
+                    vq_take_min(acc0, xx, enh + code0, code0, best, bi);
                 }
-                // first-minimum across the four lane groups that share frame f
-#pragma unroll
-                for (int m = 16; m <= 32; m <<= 1) {
-                    float od = wave_xor(best, m);
-                    int oi = wave_xor(bi, m);
-                    if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-                }
+                vq_merge_groups(best, bi);
                 if (g == 0) bidx[f * H + h] = bi;
 
                 // gather + straight-through value + squared error, in place
                 const float* qrow = cbh + bi * ES;
                 float* drow = dacc + f * d;
                 const int q4 = d >> 2;
-                for (int j = g * q4; j < (g + 1) * q4; ++j) {
-                    float xv = xr[j];
-                    float e = qrow[j] - xv;
-                    xr[j] = xv + e;
-                    float sq = e * e;
-                    drow[j] = (h == 0) ? sq : (drow[j] + sq);
-                }
+                for (int j = g * q4; j < (g + 1) * q4; ++j) vq_st(qrow[j], xr[j], h == 0 ? 0.f : drow[j], h == 0, xr[j], drow[j]);
             }
         }
 
@@ -263,13 +227,12 @@ __global__ __launch_bounds__(256) void vq_search_kernel(const float* __restrict_
                     *(f32x4*)(quant + (size_t)n * D + c4 * 4) = *(const f32x4*)(xt + row * XS + c4 * 4);
             }
             const int q4 = d >> 2;
-            const float fh = (float)H;
             for (int e = lane; e < VQ_TILE * q4; e += 64) {
                 int row = e / q4, c4 = e - row * q4;
                 int n = tile * VQ_TILE + row;
                 if (n < N) {
                     f32x4 v = *(const f32x4*)(dacc + row * d + c4 * 4);
-                    if (H > 1) { v[0] = v[0] / fh; v[1] = v[1] / fh; v[2] = v[2] / fh; v[3] = v[3] / fh; }
+                    vq_div_heads(v, H);
                     *(f32x4*)(diff + (size_t)n * d + c4 * 4) = v;
                 }
             }
@@ -289,7 +252,7 @@ __global__ __launch_bounds__(256) void vq_search_kernel(const float* __restrict_
 // next head's / tile's loads are issued before the MFMAs of the current one), feeds them as the MFMA B
 // operand while the A operand streams from the LDS codebook with 16-byte reads (one per 4 MFMAs), and
 // forms quant / diff in registers.  LDS holds only the codebook, so two workgroups share a CU.
-// fp32 summation order: channels are visited as (t, jj, g) -> 16t + 4g + jj; oracle/c/vq_oracle.c mirrors it.
+// fp32 summation order: the register form of vq_common.inc.
 // ------------------------------------------------------------------------------------------------
 template <int D4H>
 __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __restrict__ x,
@@ -309,21 +272,14 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
     const int numTiles = (N + VQ_TILE - 1) / VQ_TILE;
     const int numIters = (numTiles + nw - 1) / nw;
 
-    auto stage_group = [&](int h0, int cnt) {
-        const int rows = cnt * K, dv = d >> 2;
-        const f32x4* src = (const f32x4*)(embed_t + (size_t)h0 * K * d);
-        for (int e = threadIdx.x; e < rows * dv; e += blockDim.x) {
-            int r = e / dv, c4 = e - r * dv;
-            *(f32x4*)(cb + (size_t)r * ES + c4 * 4) = src[e];
-        }
-        for (int e = threadIdx.x; e < rows; e += blockDim.x) en[e] = enorm[(size_t)h0 * K + e];
-    };
     if (ngroups == 1) {
-        stage_group(0, H);
+        vq_stage_heads(cb, en, embed_t, enorm, 0, H, K, d, ES);
         __syncthreads();
     }
 
     f32x4 xb[D4H], xn[D4H], dacc[D4H];
+    // (the same lambda as in vq_search_stream_kernel, on purpose: as a shared helper it cost vq_search_reg_kernel<2> 16 %,
+    //  profiles/vq_search_refactor.md "The fragment load stays a lambda")
     auto load_frag = [&](f32x4 (&dst)[D4H], int tile, int h) {
         const int n = tile * VQ_TILE + f;
 #pragma unroll
@@ -345,7 +301,7 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
             const int cnt = (H - h0 < hpg) ? (H - h0) : hpg;
             if (ngroups > 1) {
                 __syncthreads();
-                stage_group(h0, cnt);
+                vq_stage_heads(cb, en, embed_t, enorm, h0, cnt, K, d, ES);
                 __syncthreads();
             }
             for (int hl = 0; hl < cnt; ++hl) {
@@ -358,16 +314,7 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
                 if (!active) continue;
                 const float* cbh = cb + (size_t)hl * K * ES;
                 const float* enh = en + hl * K;
-                float xx = 0.f;
-#pragma unroll
-                for (int t = 0; t < D4H; ++t)
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        float sq = xb[t][jj] * xb[t][jj];
-                        xx = xx + sq;
-                    }
-                xx = xx + wave_xor(xx, 16);
-                xx = xx + wave_xor(xx, 32);
+                const float xx = vq_sumsq_reg(xb);
 
                 float best = __builtin_inff();
                 int bi = 0;
@@ -376,55 +323,18 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
                 for (; ct + 2 <= ntile; ct += 2) {
                     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
                     const float* a0 = cbh + (size_t)(ct * 16 + f) * ES + 4 * g;
-                    const float* a1 = a0 + 16 * ES;
-#pragma unroll
-                    for (int t = 0; t < D4H; ++t) {
-                        const f32x4 av0 = *(const f32x4*)(a0 + 16 * t);
-                        const f32x4 av1 = *(const f32x4*)(a1 + 16 * t);
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            acc0 = mfma_f32_16x16x4(av0[jj], xb[t][jj], acc0);
-                            acc1 = mfma_f32_16x16x4(av1[jj], xb[t][jj], acc1);
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 4 * g + r;
-                        float t2 = 2.f * acc0[r];
-                        float dist = (xx - t2) + enh[code];
-                        if (dist < best) { best = dist; bi = code; }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 16 + 4 * g + r;
-                        float t2 = 2.f * acc1[r];
-                        float dist = (xx - t2) + enh[code];
-                        if (dist < best) { best = dist; bi = code; }
-                    }
+                    vq_dot_reg2(a0, a0 + 16 * ES, xb, acc0, acc1);
+                    const int code0 = ct * 16 + 4 * g;
+                    vq_take_min(acc0, xx, enh + code0, code0, best, bi);
+                    vq_take_min(acc1, xx, enh + code0 + 16, code0 + 16, best, bi);
                 }
                 if (ct < ntile) {
                     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f};
-                    const float* a0 = cbh + (size_t)(ct * 16 + f) * ES + 4 * g;
-#pragma unroll
-                    for (int t = 0; t < D4H; ++t) {
-                        const f32x4 av0 = *(const f32x4*)(a0 + 16 * t);
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) acc0 = mfma_f32_16x16x4(av0[jj], xb[t][jj], acc0);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 4 * g + r;
-                        float t2 = 2.f * acc0[r];
-                        float dist = (xx - t2) + enh[code];
-                        if (dist < best) { best = dist; bi = code; }
-                    }
+                    vq_dot_reg(cbh + (size_t)(ct * 16 + f) * ES + 4 * g, xb, acc0);
+                    const int code0 = ct * 16 + 4 * g;
+                    vq_take_min(acc0, xx, enh + code0, code0, best, bi);
                 }
-#pragma unroll
-                for (int m = 16; m <= 32; m <<= 1) {
-                    float od = wave_xor(best, m);
-                    int oi = wave_xor(bi, m);
-                    if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-                }
+                vq_merge_groups(best, bi);
                 const bool row_ok = n < N;
                 if (g == 0 && row_ok) ind[(size_t)n * H + h] = (int64_t)bi;
                 const float* qrow = cbh + (size_t)bi * ES + 4 * g;
@@ -432,24 +342,17 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
                 for (int t = 0; t < D4H; ++t) {
                     const f32x4 q4 = *(const f32x4*)(qrow + 16 * t);
                     f32x4 o4, s4;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        float e = q4[jj] - xb[t][jj];
-                        o4[jj] = xb[t][jj] + e;
-                        float sq = e * e;
-                        s4[jj] = (h == 0) ? sq : (dacc[t][jj] + sq);
-                    }
+                    vq_st_piece(q4, xb[t], dacc[t], h == 0, o4, s4);
                     dacc[t] = s4;
                     if (row_ok) *(f32x4*)(quant + (size_t)n * D + h * d + 16 * t + 4 * g) = o4;
                 }
             }
         }
         if (active && n < N) {
-            const float fh = (float)H;
 #pragma unroll
             for (int t = 0; t < D4H; ++t) {
                 f32x4 v = dacc[t];
-                if (H > 1) { v[0] = v[0] / fh; v[1] = v[1] / fh; v[2] = v[2] / fh; v[3] = v[3] / fh; }
+                vq_div_heads(v, H);
                 *(f32x4*)(diff + (size_t)n * d + 16 * t + 4 * g) = v;
             }
         }
@@ -662,19 +565,12 @@ int msmc_vq_prepare(const float* embed, float* embed_t, float* enorm, int H, int
 
 int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
                    int64_t* ind, int N, int D, int H, int K, msmc_stream stream) {
-    if (N < 0 || H <= 0 || D <= 0 || D % H) return MSMC_E_SHAPE;
+    if (vq_check_search_shape(N, D, H, K)) return MSMC_E_SHAPE;
     const int d = D / H;
-    if (d % 4 || K % 16 || K <= 0) return MSMC_E_SHAPE;
     if (N == 0) return 0;
     const bool reg_family = d % 16 == 0 && vq_use_reg_kernel;
-    if (d % 16 == 0 && vq_use_reg_kernel) {
-        const int d4h = d / 16;
-        vq_search_reg_fn rf = nullptr;
-        if (d4h == 1) rf = vq_search_reg_kernel<1>;
-        else if (d4h == 2) rf = vq_search_reg_kernel<2>;
-        else if (d4h == 4) rf = vq_search_reg_kernel<4>;
-        else if (d4h == 8) rf = vq_search_reg_kernel<8>;
-        else if (d4h == 16) rf = vq_search_reg_kernel<16>;
+    if (reg_family) {
+        vq_search_reg_fn rf = VQ_BY_D4H(vq_search_reg_kernel, d / 16);
         if (rf) {
             // most resident heads with <= 80 KiB (two workgroups per CU); at least one head must fit 160 KiB
             int hpg = H;
@@ -688,10 +584,7 @@ int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, flo
                 int rc = msmc_allow_lds((const void*)rf, (int)lds);
                 if (rc) return rc;
                 const int nw = 4;
-                const int numTiles = (N + VQ_TILE - 1) / VQ_TILE;
-                const int numIters = (numTiles + nw - 1) / nw;
-                const int wgs = (lds <= 80 * 1024 ? 2 : 1) * MSMC_NUM_CU;
-                const int grid = numIters < wgs ? numIters : wgs;
+                const int grid = vq_grid(N, nw, (lds <= 80 * 1024 ? 2 : 1) * MSMC_NUM_CU);
                 MSMC_LAUNCH(rf, dim3(grid), dim3(64 * nw), lds, (msmc_stream_t)stream, x, embed_t, enorm, quant, diff,
                             ind, N, D, H, K, hpg);
                 msmc_vq_last = msmc_prof_name("vq_search_reg_kernel");
@@ -721,9 +614,7 @@ int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, flo
     else return MSMC_E_SHAPE;
     int rc = msmc_allow_lds((const void*)fn, L.total);
     if (rc) return rc;
-    const int numTiles = (N + VQ_TILE - 1) / VQ_TILE;
-    const int numIters = (numTiles + nw - 1) / nw;
-    const int grid = numIters < MSMC_NUM_CU ? numIters : MSMC_NUM_CU;
+    const int grid = vq_grid(N, nw, MSMC_NUM_CU);
     MSMC_LAUNCH(fn, dim3(grid), dim3(64 * nw), (size_t)L.total, (msmc_stream_t)stream, x, embed_t, enorm, quant, diff,
                 ind, N, D, H, K, hpg, L);
     msmc_vq_last = msmc_prof_name("vq_search_kernel");
@@ -733,13 +624,13 @@ int msmc_vq_search(const float* x, const float* embed_t, const float* enorm, flo
 // ---- streamed search (vq_stream.inc) ---------------------------------------------------------------------------------
 int msmc_vq_search_stream(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
                           int64_t* ind, int N, int D, int H, int K, int chunk, msmc_stream stream) {
-    if (N < 0 || H <= 0 || D <= 0 || D % H) return MSMC_E_SHAPE;
-    const int d = D / H;
-    if (d % 4 || K % 16 || K <= 0) return MSMC_E_SHAPE;
+    if (vq_check_search_shape(N, D, H, K)) return MSMC_E_SHAPE;
     if (chunk < 0 || chunk % 16) return MSMC_E_SHAPE;
     if (N == 0) return 0;
-    return vq_stream_launch(x, embed_t, enorm, quant, diff, ind, N, D, H, K, chunk, d % 16 == 0 && vq_use_reg_kernel, stream);
+    return vq_stream_launch(x, embed_t, enorm, quant, diff, ind, N, D, H, K, chunk, (D / H) % 16 == 0 && vq_use_reg_kernel, stream);
 }
+
+#undef VQ_BY_D4H
 
 // ---- one wide head, any K (vq_wide.inc) --------------------------------------------------------------------------------
 int msmc_vq_search_wide(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff, int64_t* ind,
@@ -806,9 +697,7 @@ int msmc_vq_search_shortlist(const float* x, const float* embed_t, const float* 
     // in the mantissa (2^(bits - 23)), and the exact chain's own d roundings (d * 2^-24)
     const float c_approx = 3.02f / 65536.f + (float)(3 * d + 1) / 8388608.f + (float)(1u << bits) / 8388608.f +
                            (float)d / 16777216.f;
-    const int numTiles = (N + 16 * nsub - 1) / (16 * nsub);
-    const int numIters = (numTiles + nw - 1) / nw;
-    const int grid = numIters < MSMC_NUM_CU ? numIters : MSMC_NUM_CU;
+    const int grid = vq_grid(N, nw, MSMC_NUM_CU, 16 * nsub);
     MSMC_LAUNCH(fn, dim3(grid), dim3(64 * nw), lds, (msmc_stream_t)stream, x, embed_t, enorm, (const char*)image,
                 quant, diff, ind, slow_count, N, D, H, K, mode == 1 ? 1 : 0, blob, ibmask, c_approx, vqs_ablate, erows_off);
     msmc_vq_last = msmc_prof_name("vq_search_sl_kernel");

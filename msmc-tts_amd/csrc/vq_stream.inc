@@ -8,15 +8,14 @@
 // ... and wraps to head 0 for the workgroup's next 64-frame iteration, so the stream never drains inside a launch.
 //
 // A wave keeps its 16-frame tile for the whole pass over K and carries a running (best distance, best index) per lane
-// across the chunks of a head; a later codeword replaces it only on a strictly smaller distance, and the four lane groups
-// that share a frame are merged after the head's last chunk with the index as tie-break: the first minimum, as in the
-// resident kernels.  The winner rows then come from global memory (embed_t, in L2) and quant / diff are formed by the
-// resident kernels' epilogue expression.
+// across the chunks of a head (vq_take_min); the four lane groups that share a frame are merged after the head's last chunk
+// (vq_merge_groups).  The winner rows then come from global memory (embed_t, in L2) and quant / diff are formed by
+// vq_st_piece.  All of it is vq_common.inc, shared with the resident kernels.
 //
 // Two instantiation families mirror the two resident kernels, so that the fp32 summation order over the d channels -- and with
 // it every bit of the result -- is the one msmc_vq_search uses for the same shape:
-//   D4H > 0 : d = 16 * D4H, frame values in registers, channel order (t, jj, g) -> 16t + 4g + jj   (vq_search_reg_kernel)
-//   D4H = 0 : any d % 4 == 0, the current head's slice of the tile in LDS, channel order 0 .. d-1  (vq_search_kernel)
+//   D4H > 0 : d = 16 * D4H, frame values in registers: the register form of vq_common.inc          (vq_search_reg_kernel)
+//   D4H = 0 : any d % 4 == 0, the current head's slice of the tile in LDS: the LDS form            (vq_search_kernel)
 // No atomics; every global store is a vector-memory store.
 
 #define VQS_MAX_CHUNK 256            // the next chunk's norms ride in at most 4 registers of a 64-wide workgroup
@@ -65,6 +64,7 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
     };
 
     f32x4 xb[NX], xn[PREF ? NX : 1], dacc[DREG ? NX : 1];
+    // (the same lambda as in vq_search_reg_kernel, on purpose: profiles/vq_search_refactor.md "The fragment load stays a lambda")
     auto load_frag = [&](f32x4* dst, int tile, int h) {
         const int n = tile * VQ_TILE + f;
 #pragma unroll
@@ -130,14 +130,7 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
                     } else {
                         load_frag(xb, tile, h);
                     }
-                    xx = 0.f;
-#pragma unroll
-                    for (int t = 0; t < NX; ++t)
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            float sq = xb[t][jj] * xb[t][jj];
-                            xx = xx + sq;
-                        }
+                    xx = vq_sumsq_reg(xb);
                 } else {
                     float* xw = (float*)(smem + xt_off) + (size_t)w * VQ_TILE * ES;
                     for (int e = lane; e < VQ_TILE * dv; e += 64) {
@@ -148,15 +141,8 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
                         *(f32x4*)(xw + (size_t)row * ES + c4 * 4) = v;
                     }
                     wave_sync();             // tile rows were written by other lanes of this wave
-                    xx = 0.f;
-                    for (int j = g; j < d; j += 4) {
-                        float v = xr[j];
-                        float sq = v * v;
-                        xx = xx + sq;
-                    }
+                    xx = vq_sumsq_lds(xr, d, g);
                 }
-                xx = xx + wave_xor(xx, 16);
-                xx = xx + wave_xor(xx, 32);
                 best = __builtin_inff();
                 bi = 0;
             }
@@ -168,43 +154,12 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
                     const bool sg = pos < cnt;
                     if (sg) stage_load(srcn, rowsn, pos);
                     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (REG) {
-                        const float* a0 = cbc + (size_t)(ct * 16 + f) * ES + 4 * g;
-                        const float* a1 = a0 + 16 * ES;
-#pragma unroll
-                        for (int t = 0; t < NX; ++t) {
-                            const f32x4 av0 = *(const f32x4*)(a0 + 16 * t);
-                            const f32x4 av1 = *(const f32x4*)(a1 + 16 * t);
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) {
-                                acc0 = mfma_f32_16x16x4(av0[jj], xb[t][jj], acc0);
-                                acc1 = mfma_f32_16x16x4(av1[jj], xb[t][jj], acc1);
-                            }
-                        }
-                    } else {
-                        const float* a0 = cbc + (size_t)(ct * 16 + f) * ES + g;
-                        const float* a1 = a0 + 16 * ES;
-                        const float* b = xr + g;
-                        for (int s = 0; s < d; s += 4) {
-                            float bv = b[s];
-                            acc0 = mfma_f32_16x16x4(a0[s], bv, acc0);
-                            acc1 = mfma_f32_16x16x4(a1[s], bv, acc1);
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 4 * g + r;
-                        float t2 = 2.f * acc0[r];
-                        float dist = (xx - t2) + enc[code];
-                        if (dist < best) { best = dist; bi = k0 + code; }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 16 + 4 * g + r;
-                        float t2 = 2.f * acc1[r];
-                        float dist = (xx - t2) + enc[code];
-                        if (dist < best) { best = dist; bi = k0 + code; }
-                    }
+                    const float* a0 = cbc + (size_t)(ct * 16 + f) * ES + (REG ? 4 * g : g);
+                    if constexpr (REG) vq_dot_reg2(a0, a0 + 16 * ES, xb, acc0, acc1);
+                    else vq_dot_lds2(a0, a0 + 16 * ES, xr + g, d, acc0, acc1);
+                    const int code0 = ct * 16 + 4 * g;       // position in the chunk: norms by position, indices from k0
+                    vq_take_min(acc0, xx, enc + code0, k0 + code0, best, bi);
+                    vq_take_min(acc1, xx, enc + code0 + 16, k0 + code0 + 16, best, bi);
                     if (sg) {
                         stage_store(cbn, rowsn, pos);
                         pos += STG;
@@ -214,26 +169,11 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
                     const bool sg = pos < cnt;
                     if (sg) stage_load(srcn, rowsn, pos);
                     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (REG) {
-                        const float* a0 = cbc + (size_t)(ct * 16 + f) * ES + 4 * g;
-#pragma unroll
-                        for (int t = 0; t < NX; ++t) {
-                            const f32x4 av0 = *(const f32x4*)(a0 + 16 * t);
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) acc0 = mfma_f32_16x16x4(av0[jj], xb[t][jj], acc0);
-                        }
-                    } else {
-                        const float* a0 = cbc + (size_t)(ct * 16 + f) * ES + g;
-                        const float* b = xr + g;
-                        for (int s = 0; s < d; s += 4) acc0 = mfma_f32_16x16x4(a0[s], b[s], acc0);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int code = ct * 16 + 4 * g + r;
-                        float t2 = 2.f * acc0[r];
-                        float dist = (xx - t2) + enc[code];
-                        if (dist < best) { best = dist; bi = k0 + code; }
-                    }
+                    const float* a0 = cbc + (size_t)(ct * 16 + f) * ES + (REG ? 4 * g : g);
+                    if constexpr (REG) vq_dot_reg(a0, xb, acc0);
+                    else vq_dot_lds(a0, xr + g, d, acc0);
+                    const int code0 = ct * 16 + 4 * g;
+                    vq_take_min(acc0, xx, enc + code0, k0 + code0, best, bi);
                     if (sg) {
                         stage_store(cbn, rowsn, pos);
                         pos += STG;
@@ -252,12 +192,7 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
             }
 
             if (c == nch - 1) {   // the head's last chunk: first minimum over the four lane groups, then the epilogue
-#pragma unroll
-                for (int m = 16; m <= 32; m <<= 1) {
-                    float od = wave_xor(best, m);
-                    int oi = wave_xor(bi, m);
-                    if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-                }
+                vq_merge_groups(best, bi);
                 if (g == 0 && row_ok) ind[(size_t)n * H + h] = (int64_t)bi;
                 const float* qrow = embed_t + ((size_t)h * K + bi) * d;          // winner row from global memory (L2)
                 if constexpr (REG) {
@@ -269,18 +204,11 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
                         float* dp = diff + (size_t)n * d + 16 * t + 4 * g;      // (DREG false: read and written by this lane alone)
                         if constexpr (DREG) p4 = dacc[t];
                         else if (h > 0 && row_ok) p4 = *(const f32x4*)dp;
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) {
-                            float e = q4[jj] - xb[t][jj];
-                            o4[jj] = xb[t][jj] + e;
-                            float sq = e * e;
-                            s4[jj] = (h == 0) ? sq : (p4[jj] + sq);
-                        }
+                        vq_st_piece(q4, xb[t], p4, h == 0, o4, s4);
                         if constexpr (DREG) {
                             dacc[t] = s4;
                         } else {
-                            const float fh = (float)H;
-                            if (H > 1 && h == H - 1) { s4[0] = s4[0] / fh; s4[1] = s4[1] / fh; s4[2] = s4[2] / fh; s4[3] = s4[3] / fh; }
+                            if (h == H - 1) vq_div_heads(s4, H);
                             if (row_ok) *(f32x4*)dp = s4;
                         }
                         if (row_ok) *(f32x4*)(quant + (size_t)n * D + h * d + 16 * t + 4 * g) = o4;
@@ -288,22 +216,15 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
                 } else {
                     // this lane owns the 16-byte pieces g, g + 4, ... of its frame; the per-head sum of squares lives in diff
                     // itself (read and written by this lane alone), divided by H with the last head
-                    const float fh = (float)H;
                     if (row_ok)
                         for (int c4 = g; c4 < dv; c4 += 4) {
                             const f32x4 q4 = *(const f32x4*)(qrow + 4 * c4);
                             const f32x4 x4 = *(const f32x4*)(xr + 4 * c4);
                             float* dp = diff + (size_t)n * d + 4 * c4;
-                            f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, o4;
-                            if (h > 0) s4 = *(const f32x4*)dp;
-#pragma unroll
-                            for (int jj = 0; jj < 4; ++jj) {
-                                float e = q4[jj] - x4[jj];
-                                o4[jj] = x4[jj] + e;
-                                float sq = e * e;
-                                s4[jj] = (h == 0) ? sq : (s4[jj] + sq);
-                                if (H > 1 && h == H - 1) s4[jj] = s4[jj] / fh;
-                            }
+                            f32x4 p4 = {0.f, 0.f, 0.f, 0.f}, s4, o4;
+                            if (h > 0) p4 = *(const f32x4*)dp;
+                            vq_st_piece(q4, x4, p4, h == 0, o4, s4);
+                            if (h == H - 1) vq_div_heads(s4, H);
                             *(f32x4*)dp = s4;
                             *(f32x4*)(quant + (size_t)n * D + h * d + 4 * c4) = o4;
                         }
@@ -317,11 +238,10 @@ __global__ __launch_bounds__(256, D4H > 0 ? 2 : 1) void vq_search_stream_kernel(
         }
         if constexpr (DREG) {
             if (row_ok) {
-                const float fh = (float)H;
 #pragma unroll
                 for (int t = 0; t < NX; ++t) {
                     f32x4 v = dacc[t];
-                    if (H > 1) { v[0] = v[0] / fh; v[1] = v[1] / fh; v[2] = v[2] / fh; v[3] = v[3] / fh; }
+                    vq_div_heads(v, H);
                     *(f32x4*)(diff + (size_t)n * d + 16 * t + 4 * g) = v;
                 }
             }
@@ -342,16 +262,10 @@ static int vq_stream_launch(const float* x, const float* embed_t, const float* e
     const int d = D / H;
     if (chunk < 0 || chunk % 16 || chunk > VQS_MAX_CHUNK) return MSMC_E_SHAPE;
     if ((double)N * D * 4.0 >= 4294967296.0) return MSMC_E_SHAPE;     // (32-bit frame byte offsets, as the shortlist launcher)
-    vq_search_stream_fn fn = vq_search_stream_kernel<0>;
-    if (reg && d % 16 == 0) {
-        const int d4h = d / 16;
-        if (d4h == 1) fn = vq_search_stream_kernel<1>;
-        else if (d4h == 2) fn = vq_search_stream_kernel<2>;
-        else if (d4h == 4) fn = vq_search_stream_kernel<4>;
-        else if (d4h == 8) fn = vq_search_stream_kernel<8>;
-        else if (d4h == 16) fn = vq_search_stream_kernel<16>;
-    }
-    const bool lds_tile = fn == (vq_search_stream_fn)vq_search_stream_kernel<0>;
+    vq_search_stream_fn fn = nullptr;
+    if (reg && d % 16 == 0) fn = VQ_BY_D4H(vq_search_stream_kernel, d / 16);
+    const bool lds_tile = !fn;
+    if (lds_tile) fn = vq_search_stream_kernel<0>;
     // LDS-tile family: the widest workgroup whose tile slices leave room for two 16-codeword buffers
     int nw = 4;
     size_t xt = 0;
@@ -374,10 +288,7 @@ static int vq_stream_launch(const float* x, const float* embed_t, const float* e
     if (lds > VQ_LDS_LIMIT) return MSMC_E_SHAPE;
     int rc = msmc_allow_lds((const void*)fn, (int)lds);
     if (rc) return rc;
-    const int numTiles = (N + VQ_TILE - 1) / VQ_TILE;
-    const int numIters = (numTiles + nw - 1) / nw;
-    const int wgs = (lds <= 80 * 1024 ? 2 : 1) * MSMC_NUM_CU;
-    const int grid = numIters < wgs ? numIters : wgs;
+    const int grid = vq_grid(N, nw, (lds <= 80 * 1024 ? 2 : 1) * MSMC_NUM_CU);
     MSMC_LAUNCH(fn, dim3(grid), dim3(64 * nw), lds, (msmc_stream_t)stream, x, embed_t, enorm, quant, diff, ind, N, D, H, K,
                 Kc, (int)vqst_chunk_bytes(d, Kc));
     msmc_vq_last = msmc_prof_name("vq_search_stream_kernel");

@@ -152,12 +152,7 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* x, con
     }
 
     // first minimum over the four lane groups of a frame, then over the WC waves that share it
-#pragma unroll
-    for (int m = 16; m <= 32; m <<= 1) {
-        float od = wave_xor(best, m);
-        int oi = wave_xor(bi, m);
-        if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-    }
+    vq_merge_groups(best, bi);
     if constexpr (WC > 1) {
         if (g == 0) {
             mb[wc * FT + wf * 16 + f] = best;

@@ -70,7 +70,8 @@ def test_weight_images_in_one_tiled_pass_match_the_definition():
 
 @pytest.mark.parametrize('shortlist', [None, True, False], ids=['product', 'shortlist-kernel', 'exact-kernel'])
 @pytest.mark.parametrize('H,K,D,N', [(1, 64, 256, 777), (4, 64, 256, 6400), (4, 256, 256, 1600), (8, 512, 256, 530),
-                                     (4, 16, 32, 51), (2, 48, 24, 1), (4, 64, 256, 16), (4, 64, 256, 17)])
+                                     (4, 16, 32, 51), (2, 48, 24, 1), (4, 64, 256, 16), (4, 64, 256, 17),
+                                     (2, 48, 64, 37), (4, 512, 80, 37)])
 def test_vq_search_bit_exact_vs_c_oracle(H, K, D, N, shortlist):
     """``product``: the kernel the product picks for the shape and size; ``shortlist-kernel``: csrc/vq_shortlist.inc forced
     (d in {32, 64}; skipped elsewhere); ``exact-kernel``: the register-resident / LDS-tile exact kernels forced"""

@@ -44,6 +44,8 @@ def test_predictor_step_matches_reference():
     (1, 64, 256, 100),     # single head, d=256: falls back to 2-wave workgroups
     (8, 64, 64, 333),      # d=8; several persistent iterations per workgroup (interpreter has 3 "CUs")
     (2, 48, 24, 1),        # odd tile count of codewords, single frame
+    (2, 48, 64, 37),       # register kernel, d=32: one pair step of 16-codeword tiles plus the tail step
+    (4, 512, 80, 37),      # LDS-tile kernel, d=20: the codebook staged in two head groups
 ])
 def test_vq_search_shapes_bit_exact_vs_c_oracle(H, K, D, N):
     import numpy as np
