@@ -127,7 +127,39 @@ int msmc_vq_backward(const float* g_quant, const float* g_diff, const float* x, 
                      float* gx, int N, int D, int H, msmc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
- * G1/G2/D1/D2  channels-last implicit-GEMM convolution family on the matrix cores.
+ * KM  the M step of Lloyd's algorithm for the k-means unit codebooks of KMeansVQGANEmb (msmc-tts_amd/csrc/kmeans.hip;
+ * the E step is msmc_vq_prepare + msmc_vq_search_wide; the loop is msmctts_amd/hip/kmeans.py fit_kmeans).
+ * No reference counterpart: the reference loads a k-means model fitted elsewhere (msmc_vqgan_emb.py:294-336).
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of scratch msmc_kmeans_stats needs for these sizes: 4 (P K + 2 (K + 1) + N) rounded up to 16, with P <= 256 parts
+ * and P K <= N + K, plus 4 d (N / 64 + min(K, N)) for the run partials.  0 for N <= 0 or a shape the kernel refuses. */
+size_t msmc_kmeans_stats_workspace(int N, int d, int K);
+
+/* Per-centroid sums and counts of labelled frames: x [N][d], ind [N] -> sums [K][d], counts [K] (fp32; exact below 2^24
+ * rows per centroid).  sums[k] = sum of the rows n with ind[n] == k, counts[k] = their number; entries of ind outside
+ * [0, K) are skipped (the mask for padding).  accumulate = 0 overwrites sums / counts, accumulate = 1 adds this call's
+ * totals onto what they hold, one add per element (blocks of frames folded in a fixed order).
+ * Deterministic, no floating-point atomics.  Summation order, per channel: the rows of centroid k in ascending n are cut
+ * into runs of 64 rows; a run partial is (((+0 + x[n_0]) + x[n_1]) + ...) over its rows in ascending n; the centroid's
+ * total is (((+0 + partial_0) + partial_1) + ...) over its runs in ascending order; sums[k] = total, or sums[k] + total with
+ * accumulate.  An empty centroid has total +0 and count 0.
+ * Takes d % 4 == 0, 4 <= d <= 2048, K >= 1, N >= 0, N * d * 4 < 2^32 and x, sums, workspace 16-byte aligned: MSMC_E_SHAPE
+ * otherwise, nothing launched.  MSMC_E_WORKSPACE for a workspace below msmc_kmeans_stats_workspace.  N == 0: returns 0 and,
+ * without accumulate, writes zeros (no workspace needed). */
+int msmc_kmeans_stats(const float* x, const int64_t* ind, float* sums, float* counts, void* workspace, size_t workspace_bytes,
+                      int N, int d, int K, int accumulate, msmc_stream stream);
+
+/* Centre update, in place: centers[k][c] = sums[k][c] / counts[k] (IEEE fp32 division) where counts[k] > 0; an empty
+ * centroid keeps its row.  shift2[k] = squared movement of row k (+0 for an empty centroid), summed in a fixed order: lane l
+ * of a 64-lane wave adds (new - old)^2 of the 4-channel pieces l, l + 64, l + 128, ... in ascending channel order from +0,
+ * then the 64 lane sums are added as a butterfly, v = v + v[lane ^ m] for m = 1, 2, 4, 8, 16, 32.
+ * Takes d % 4 == 0, 4 <= d <= 2048, K >= 1, sums / centers 16-byte aligned (MSMC_E_SHAPE otherwise). */
+int msmc_kmeans_update(const float* sums, const float* counts, float* centers, float* shift2, int d, int K,
+                       msmc_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * G1/G2/D1/D2 channels-last implicit-GEMM convolution family on the matrix cores.
  * Replaces the cuDNN/MIOpen convolutions behind
  *   Generator.forward / ResBlock1.forward   reference msmctts/networks/hifigan/generator.py:40-55, common.py:44-51
  *   DiscriminatorP.forward                  reference msmctts/networks/hifigan/discriminator.py:135-154

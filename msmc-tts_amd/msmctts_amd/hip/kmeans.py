@@ -1,0 +1,201 @@
+"""Fitting the k-means unit codebook of ``KMeansVQGANEmb`` on the gfx950 kernels: Lloyd's algorithm over frames [N, d].
+
+The E step is the search the model itself runs (``vq.vq_prepare`` + ``vq.vq_search``: at unit widths ``msmc_vq_search_wide``,
+csrc/vq_wide.inc); the M step is csrc/kmeans.hip: ``msmc_kmeans_stats`` (per-centroid sums and counts in a fixed summation
+order, no floating-point atomics) and ``msmc_kmeans_update`` (the division and each centre's squared movement).  The reference
+has no counterpart: it loads a model somebody fitted elsewhere (msmc_vqgan_emb.py:294-336).  ``fit_kmeans(...).save(path)``
+writes the ``.npy`` of centres [K, d] that ``KMeansQuantizer`` reads.
+
+There is no CPU path and no fallback: shapes the kernels refuse raise with the launcher's code, host tensors are uploaded
+block by block, and without the library (or with a host ``device`` on the product build) the calls raise.
+"""
+import numpy as np
+import torch
+
+from . import lib
+from . import vq as hipvq
+
+
+def _workspace(N, d, K, device, workspace=None):
+    need = int(lib.get().msmc_kmeans_stats_workspace(N, d, K))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+    return workspace
+
+
+def centroid_stats(x, ind, K, out=None, accumulate=False, workspace=None):
+    """x [N, d] fp32, ind [N] int64 -> (sums [K, d], counts [K]) of the rows of every centroid; entries of ``ind`` outside
+    [0, K) are skipped.  ``out``: a (sums, counts) pair to write, or with ``accumulate`` to add this call's totals onto (one add
+    per element).  Deterministic; the summation order is documented at ``msmc_kmeans_stats`` (include/msmc_hip.h)."""
+    N, d = x.shape
+    K = int(K)
+    if out is None:
+        if accumulate:
+            raise ValueError('accumulate needs the (sums, counts) pair to add onto')
+        out = (torch.empty((max(K, 0), d), dtype=torch.float32, device=x.device),
+               torch.empty((max(K, 0),), dtype=torch.float32, device=x.device))
+    sums, counts = out
+    if K >= 1 and (tuple(sums.shape) != (K, d) or tuple(counts.shape) != (K,)):
+        raise ValueError('out: sums [%d, %d] and counts [%d], got %s and %s' % (K, d, K, tuple(sums.shape), tuple(counts.shape)))
+    xc = x.detach().contiguous()
+    indc = ind.reshape(-1).contiguous()
+    if indc.numel() != N:
+        raise ValueError('%d labels for %d frames' % (indc.numel(), N))
+    workspace = _workspace(N, d, K, x.device, workspace)
+    lib.check(lib.get().msmc_kmeans_stats(lib.ptr(xc, torch.float32), lib.ptr(indc, torch.int64), lib.ptr(sums, torch.float32),
+                                          lib.ptr(counts, torch.float32), lib.ptr(workspace),
+                                          workspace.numel() * workspace.element_size(), N, d, K, int(bool(accumulate)),
+                                          lib.stream(xc)), 'msmc_kmeans_stats')
+    return sums, counts
+
+
+def centroid_update(sums, counts, centers):
+    """centers [K, d] in place: ``sums[k] / counts[k]`` where ``counts[k] > 0``, an empty centroid keeps its row; returns
+    shift2 [K], the squared movement of every row (zero for an empty centroid)"""
+    K, d = centers.shape
+    shift2 = torch.empty((K,), dtype=torch.float32, device=centers.device)
+    lib.check(lib.get().msmc_kmeans_update(lib.ptr(sums, torch.float32), lib.ptr(counts, torch.float32),
+                                           lib.ptr(centers, torch.float32), lib.ptr(shift2), d, K, lib.stream(centers)),
+              'msmc_kmeans_update')
+    return shift2
+
+
+class KMeansFit(object):
+    """what ``fit_kmeans`` returns.  ``cluster_centers_`` [K, d] float32, ``labels_`` [N] int64 and ``inertia_``: the
+    assignment of the frames to the RETURNED centres (a final search) and its summed squared error; ``n_iter_``: Lloyd
+    iterations run; ``counts_`` [K] int64 and ``step_labels_`` [N] int64: the rows per centroid and the labels of the last M
+    step, the one the returned centres are the means of (where the fit stopped because no label changed they are ``labels_``);
+    ``history_``: per iteration ``{'inertia', 'empty', 'shift', 'changed'}`` -- the E step's summed squared error, the
+    number of empty centroids, the summed squared movement of the centres and whether a label changed."""
+
+    def __init__(self, centers, labels, inertia, n_iter, counts, step_labels, history):
+        self.cluster_centers_, self.labels_, self.inertia_, self.n_iter_ = centers, labels, inertia, n_iter
+        self.counts_, self.step_labels_, self.history_ = counts, step_labels, history
+
+    def save(self, path):
+        """the centres as the ``.npy`` [K, d] that ``KMeansQuantizer`` / ``KMeansVQGANEmb(quantizer_path=...)`` load"""
+        path = str(path)
+        if not path.endswith('.npy'):
+            raise ValueError('%s: the centroid file is recognised by its .npy suffix' % path)
+        with open(path, 'wb') as fout:
+            np.save(fout, self.cluster_centers_, allow_pickle=False)
+        return path
+
+
+def default_block_frames(d):
+    """the largest block with block * d * 4 < 2^31 (the search kernels address a block's frames with 32-bit byte offsets)"""
+    return max(1, ((1 << 31) - 1) // (4 * d))
+
+
+def _rows(frames, s, e, device):
+    xb = frames[s:e] if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames[s:e]))
+    return xb.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _mean_variance(frames, spans, device):
+    """mean over the channels of the per-channel (population) variance of the frames, float64 sums over slabs of a block"""
+    N, d = frames.shape
+    s1 = torch.zeros(d, dtype=torch.float64, device=device)
+    s2 = torch.zeros(d, dtype=torch.float64, device=device)
+    for s, e in spans:
+        for slab in _rows(frames, s, e, device).split(1 << 16):
+            v = slab.double()
+            s1 += v.sum(0)
+            s2 += (v * v).sum(0)
+    mean = s1 / N
+    return float((s2 / N - mean * mean).clamp_(min=0).mean())
+
+
+def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, block_frames=None, device=None, callback=None):
+    """Lloyd's algorithm on the gfx950 kernels -> ``KMeansFit``.
+
+    ``frames``: a device tensor, host tensor or numpy array [N, d] fp32, processed in blocks of ``block_frames`` frames
+    (default: the largest block with block * d * 4 < 2^31); host data is uploaded block by block in every iteration, to
+    ``device`` (default: the current GPU; a device tensor stays where it is).  ``init``: the first centres [K, d]; None draws K
+    distinct frames with ``torch.Generator().manual_seed(seed)`` on the host (k-means++ seeding is out of scope: pass its result
+    as ``init``).  Every iteration prepares the centres (``vq_prepare``), then per block, in block order, searches
+    (``vq_search``: labels and squared error) and accumulates the centroid statistics, then updates the centres
+    (``msmc_kmeans_update``; an empty centroid keeps its row -- it is not relocated) and reads back, once, the summed squared
+    movement of the centres, the inertia (the search's squared error summed in float64), whether a label changed and the
+    number of empty centroids.  It stops when no label changed, when the movement is at most ``tol`` times the mean per-channel
+    variance of the frames (scikit-learn's meaning of ``tol``), or after ``max_iter`` iterations.  Same inputs, same bits:
+    every sum runs in a fixed order.  ``callback(iteration, record)`` is called with every ``history_`` record."""
+    if not torch.is_tensor(frames):
+        frames = np.asarray(frames)
+    if len(frames.shape) != 2:
+        raise ValueError('frames: expected [N, d], got %s' % (tuple(frames.shape),))
+    N, d = int(frames.shape[0]), int(frames.shape[1])
+    K = int(n_clusters)
+    if max_iter < 1:
+        raise ValueError('max_iter must be at least 1')
+    if N < 1 or K < 1:
+        raise ValueError('fit_kmeans needs at least one frame and one cluster (got N = %d, n_clusters = %d)' % (N, K))
+    if torch.is_tensor(frames) and frames.is_cuda:
+        device = frames.device
+    else:
+        device = torch.device('cuda' if device is None else device)
+    block = default_block_frames(d) if block_frames is None else int(block_frames)
+    if block < 1:
+        raise ValueError('block_frames must be positive')
+    spans = [(s, min(N, s + block)) for s in range(0, N, block)]
+
+    if init is None:
+        if not 1 <= K <= N:
+            raise ValueError('n_clusters = %d: cannot draw that many distinct frames from %d' % (K, N))
+        pick = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:K]
+        if torch.is_tensor(frames):
+            centers = frames[pick.to(frames.device)]
+        else:
+            centers = torch.from_numpy(np.ascontiguousarray(frames[pick.numpy()]))
+    else:
+        centers = torch.as_tensor(np.asarray(init) if not torch.is_tensor(init) else init)
+        if tuple(centers.shape) != (K, d):
+            raise ValueError('init: expected [%d, %d], got %s' % (K, d, tuple(centers.shape)))
+    centers = centers.detach().to(device=device, dtype=torch.float32).contiguous().clone()
+
+    with torch.no_grad():
+        limit = float(tol) * _mean_variance(frames, spans, device) if tol > 0 else 0.0
+        sums = torch.empty((K, d), dtype=torch.float32, device=device)
+        counts = torch.empty((K,), dtype=torch.float32, device=device)
+        workspace = _workspace(min(N, block), d, K, device)
+
+        def prepared():
+            return hipvq.vq_prepare(centers.t().unsqueeze(0).contiguous(), frames=min(N, block))
+
+        def e_step(embed_t, enorm, labels, stats):
+            inertia = torch.zeros((), dtype=torch.float64, device=device)
+            for b, (s, e) in enumerate(spans):
+                xb = _rows(frames, s, e, device)
+                _, diff, ind = hipvq.vq_search(xb, embed_t, enorm)
+                ind = ind.reshape(-1)
+                inertia += diff.sum(dtype=torch.float64)
+                labels[s:e] = ind
+                if stats:
+                    centroid_stats(xb, ind, K, out=(sums, counts), accumulate=b > 0, workspace=workspace)
+            return inertia
+
+        labels = torch.full((N,), -1, dtype=torch.int64, device=device)
+        previous = torch.full((N,), -1, dtype=torch.int64, device=device)
+        history, changed, n_iter = [], True, 0
+        for it in range(int(max_iter)):
+            labels, previous = previous, labels
+            inertia = e_step(*prepared(), labels, True)
+            shift2 = centroid_update(sums, counts, centers)
+            back = torch.stack([shift2.sum(dtype=torch.float64), inertia, (labels != previous).any().double(),
+                                (counts == 0).sum().double()]).cpu()           # the iteration's one read-back
+            shift, changed = float(back[0]), bool(back[2] != 0)
+            history.append({'inertia': float(back[1]), 'empty': int(back[3]), 'shift': shift, 'changed': changed})
+            n_iter = it + 1
+            if callback is not None:
+                callback(n_iter, history[-1])
+            if not changed or shift <= limit:
+                break
+        step_labels = labels
+        if changed:             # the centres moved after the last search: the assignment to the returned centres
+            final = torch.empty_like(labels)
+            inertia = float(e_step(*prepared(), final, False))
+        else:                   # the same labels gave the same sums, hence the same centres, bit for bit: that search stands
+            final, inertia = labels, history[-1]['inertia']
+        hipvq._F32_OF['last'] = None            # (the search keeps its last block of frames for an EMA update that never comes)
+        return KMeansFit(centers.cpu().numpy(), final.cpu().numpy(), inertia, n_iter, counts.cpu().numpy().astype(np.int64),
+                         step_labels.cpu().numpy(), history)

@@ -23,7 +23,8 @@ the optional global encoder and frame decoder and the vocoder.  Same class names
 ``mel_predictor``) and output-dictionary keys (``encoder_indices``, ``mel_outputs``, ``decoder_outputs``); ``forward`` takes the
 ``window`` / ``window_frames`` forms of ``MSMCVQGANEmb.forward``.  ``quantizer_path`` is a pickle holding an object with
 ``cluster_centers_`` [K, d] as in the reference (unpickling a scikit-learn model needs scikit-learn installed; nothing here
-imports it) or, in addition, a ``.npy`` file of shape [K, d].  Deviations from the reference:
+imports it) or, in addition, a ``.npy`` file of shape [K, d] -- which ``fit_kmeans`` (hip/kmeans.py, exported here: Lloyd's
+algorithm on the gfx950 kernels) produces from frames [N, d].  Deviations from the reference:
 
 * the reference assigns ``embed`` from the file at every forward (:316), so a checkpoint's ``embed`` never counts.  Here the
   centroids are copied into the buffer at construction and again after every ``load_state_dict``: the same observable result;
@@ -43,6 +44,7 @@ import torch.nn.functional as F
 
 from ...hip import norm as hipnorm
 from ...hip import window as hipwindow
+from ...hip.kmeans import fit_kmeans  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
 from .modules import Quantize
