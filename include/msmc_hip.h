@@ -158,6 +158,29 @@ int msmc_kmeans_stats(const float* x, const int64_t* ind, float* sums, float* co
 int msmc_kmeans_update(const float* sums, const float* counts, float* centers, float* shift2, int d, int K,
                        msmc_stream stream);
 
+/* Bytes of scratch msmc_kmeanspp_seed needs: 128 of state, float64 prefixes 8 L (T + 1) and tile partials 8 L T (each rounded
+ * up to 16) with T = ceil(N / 256) tiles, and two buffers of minima 4 L N (each rounded up to 16).  0 for a shape the
+ * kernels refuse. */
+size_t msmc_kmeanspp_workspace(int N, int d, int K, int L);
+
+/* Greedy k-means++ seeding (msmc-tts_amd/csrc/kmeans_pp.hip): K frames of x [N][d] as the first centres of Lloyd's
+ * algorithm.  centre 0 = x[first], mind[n] = |x[n] - centre 0|^2; step i = 1 .. K - 1 draws L candidates, candidate j = the
+ * first frame n with cum[n] > u[i - 1][j] * total (cum: the running sum of mind, total its last value; u [K - 1][L] float64 in
+ * [0, 1)), evaluates pot[j] = sum over n of min(mind[n], |x[n] - x[candidate j]|^2) for all of them in ONE pass over x, and
+ * keeps the candidate of the smallest pot (ties: the lowest j): its row is centre i, mind takes the minimum with its distances.
+ * Outputs: centers [K][d] (the chosen rows), chosen [K] (their frame numbers), potential [K] (the sum of mind after every
+ * pick).  Enqueues everything -- two launches per centre -- on the stream: no read-back, no allocation.
+ * Fixed order of every sum (same inputs, same bits): distances in fp32 as the direct difference, per frame in the order of
+ * shift2 above; cum, total and pot in float64: within a tile of 256 frames local[n] = ((+0 + m[n0]) + ...) + m[n] in
+ * ascending n, pre[t + 1] = pre[t] + local[last frame of tile t] over the tiles in ascending order from +0, cum[n] =
+ * pre[t] + local[n], total = pot = pre[T].  cum never decreases and ends at total bit for bit; a frame of weight 0 is never
+ * picked; total == 0 (every frame coincides with a centre, e.g. K > N) picks frame N - 1: duplicate centres.
+ * Takes d % 4 == 0, 4 <= d <= 2048, K >= 1, 1 <= L <= 16, 1 <= N < 2^31, 0 <= first < N, x / centers / workspace 16-byte
+ * aligned (rows are addressed with 64-bit offsets: N d 4 may exceed 2^32): MSMC_E_SHAPE otherwise, nothing launched.
+ * MSMC_E_WORKSPACE for a workspace below msmc_kmeanspp_workspace. */
+int msmc_kmeanspp_seed(const float* x, int N, int d, int K, int L, long first, const double* u, float* centers, int64_t* chosen,
+                       double* potential, void* workspace, size_t workspace_bytes, msmc_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * G1/G2/D1/D2 channels-last implicit-GEMM convolution family on the matrix cores.
  * Replaces the cuDNN/MIOpen convolutions behind

@@ -60,17 +60,74 @@ def centroid_update(sums, counts, centers):
     return shift2
 
 
+MAX_LOCAL_TRIALS = 16                       # KPP_MAX_L of csrc/kmeans_pp.hip
+
+
+def default_local_trials(K):
+    """scikit-learn's ``2 + floor(ln K)`` candidates per seeding step, capped at what the kernel takes"""
+    return min(MAX_LOCAL_TRIALS, 2 + int(np.log(K)))
+
+
+def kmeans_plusplus(frames, n_clusters, seed=0, n_local_trials=None, first=None, uniforms=None, device=None):
+    """Greedy k-means++ seeding on the gfx950 kernels (``msmc_kmeanspp_seed``, csrc/kmeans_pp.hip) -> ``(centers [K, d]
+    float32, chosen [K] int64, potential [K] float64)``, tensors on the device: the chosen rows of ``frames``, their frame
+    numbers, and the summed squared distance of every frame to its nearest centre after each pick.
+
+    Centre 0 is frame ``first``; every further step draws ``n_local_trials`` candidates (default ``2 + floor(ln K)``, at most
+    16) with probability proportional to the squared distance to the nearest centre so far -- candidate j of step i is the
+    first frame whose running sum of those distances exceeds ``uniforms[i - 1, j]`` times their total -- and keeps the one
+    that lowers the total most.  ``first`` and ``uniforms`` [K - 1, n_local_trials] float64 in [0, 1) default to
+    ``randint(N)`` and ``rand(K - 1, n_local_trials, dtype=float64)`` drawn in that order from
+    ``torch.Generator().manual_seed(seed)`` on the host.  A device tensor is seeded over all its frames where it lies; host
+    frames are uploaded once, whole.  The whole seeding is enqueued without a read-back; every sum runs in a fixed order
+    (include/msmc_hip.h), so the same inputs give the same bits."""
+    if not torch.is_tensor(frames):
+        frames = torch.from_numpy(np.ascontiguousarray(np.asarray(frames), dtype=np.float32))
+    if frames.dim() != 2:
+        raise ValueError('frames: expected [N, d], got %s' % (tuple(frames.shape),))
+    N, d = int(frames.shape[0]), int(frames.shape[1])
+    K = int(n_clusters)
+    if N < 1 or K < 1:
+        raise ValueError('kmeans_plusplus needs at least one frame and one cluster (got N = %d, n_clusters = %d)' % (N, K))
+    L = default_local_trials(K) if n_local_trials is None else int(n_local_trials)
+    if frames.is_cuda:
+        device = frames.device
+    else:
+        device = torch.device('cuda' if device is None else device)
+    gen = torch.Generator().manual_seed(int(seed))
+    drawn = int(torch.randint(N, (1,), generator=gen))
+    first = drawn if first is None else int(first)
+    if uniforms is None:
+        uniforms = torch.rand(max(K - 1, 0), max(L, 0), dtype=torch.float64, generator=gen)
+    uniforms = torch.as_tensor(uniforms, dtype=torch.float64)
+    if tuple(uniforms.shape) != (K - 1, L):
+        raise ValueError('uniforms: expected [%d, %d], got %s' % (K - 1, L, tuple(uniforms.shape)))
+    x = frames.detach().to(device=device, dtype=torch.float32).contiguous()
+    u = uniforms.to(device).contiguous()
+    centers = torch.empty((K, d), dtype=torch.float32, device=device)
+    chosen = torch.empty((K,), dtype=torch.int64, device=device)
+    potential = torch.empty((K,), dtype=torch.float64, device=device)
+    L_ = lib.get()
+    need = int(L_.msmc_kmeanspp_workspace(N, d, K, L))
+    workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+    lib.check(L_.msmc_kmeanspp_seed(lib.ptr(x, torch.float32), N, d, K, L, first, lib.ptr(u, torch.float64),
+                                    lib.ptr(centers), lib.ptr(chosen), lib.ptr(potential), lib.ptr(workspace), need,
+                                    lib.stream(x)), 'msmc_kmeanspp_seed')
+    return centers, chosen, potential
+
+
 class KMeansFit(object):
     """what ``fit_kmeans`` returns.  ``cluster_centers_`` [K, d] float32, ``labels_`` [N] int64 and ``inertia_``: the
     assignment of the frames to the RETURNED centres (a final search) and its summed squared error; ``n_iter_``: Lloyd
     iterations run; ``counts_`` [K] int64 and ``step_labels_`` [N] int64: the rows per centroid and the labels of the last M
     step, the one the returned centres are the means of (where the fit stopped because no label changed they are ``labels_``);
     ``history_``: per iteration ``{'inertia', 'empty', 'shift', 'changed'}`` -- the E step's summed squared error, the
-    number of empty centroids, the summed squared movement of the centres and whether a label changed."""
+    number of empty centroids, the summed squared movement of the centres and whether a label changed; ``init_indices_`` [K]
+    int64: the frame numbers in ``frames`` of the first centres, None where ``init`` was an array."""
 
-    def __init__(self, centers, labels, inertia, n_iter, counts, step_labels, history):
+    def __init__(self, centers, labels, inertia, n_iter, counts, step_labels, history, init_indices=None):
         self.cluster_centers_, self.labels_, self.inertia_, self.n_iter_ = centers, labels, inertia, n_iter
-        self.counts_, self.step_labels_, self.history_ = counts, step_labels, history
+        self.counts_, self.step_labels_, self.history_, self.init_indices_ = counts, step_labels, history, init_indices
 
     def save(self, path):
         """the centres as the ``.npy`` [K, d] that ``KMeansQuantizer`` / ``KMeansVQGANEmb(quantizer_path=...)`` load"""
@@ -106,14 +163,41 @@ def _mean_variance(frames, spans, device):
     return float((s2 / N - mean * mean).clamp_(min=0).mean())
 
 
-def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, block_frames=None, device=None, callback=None):
+def _seed_plusplus(frames, N, K, seed, n_local_trials, seed_frames, device):
+    """the first centres of ``fit_kmeans(init='k-means++')`` -> (centres [K, d] on the device, frame numbers [K] int64 numpy)"""
+    on_device = torch.is_tensor(frames) and frames.is_cuda
+    if seed_frames is None:
+        M = N if on_device else min(N, 256 * K)
+    else:
+        M = min(N, int(seed_frames))
+        if M < 1:
+            raise ValueError('seed_frames must be positive')
+    rows = None
+    if M < N:
+        rows = torch.sort(torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:M]).values
+        if torch.is_tensor(frames):
+            frames = frames[rows.to(frames.device)]
+        else:
+            frames = torch.from_numpy(np.ascontiguousarray(frames[rows.numpy()]))
+    centers, chosen, _ = kmeans_plusplus(frames, K, seed=seed, n_local_trials=n_local_trials, device=device)
+    chosen = chosen.cpu()
+    return centers, (chosen if rows is None else rows[chosen]).numpy()
+
+
+def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, block_frames=None, device=None, callback=None,
+               n_local_trials=None, seed_frames=None):
     """Lloyd's algorithm on the gfx950 kernels -> ``KMeansFit``.
 
     ``frames``: a device tensor, host tensor or numpy array [N, d] fp32, processed in blocks of ``block_frames`` frames
     (default: the largest block with block * d * 4 < 2^31); host data is uploaded block by block in every iteration, to
     ``device`` (default: the current GPU; a device tensor stays where it is).  ``init``: the first centres [K, d]; None draws K
-    distinct frames with ``torch.Generator().manual_seed(seed)`` on the host (k-means++ seeding is out of scope: pass its result
-    as ``init``).  Every iteration prepares the centres (``vq_prepare``), then per block, in block order, searches
+    distinct frames with ``torch.Generator().manual_seed(seed)`` on the host; ``'k-means++'`` seeds them on the card
+    (``kmeans_plusplus`` with ``seed`` and ``n_local_trials``) -- a device tensor over all its frames; host frames over a
+    sample of ``seed_frames`` rows (drawn as the first ``seed_frames`` of ``randperm(N)`` from
+    ``torch.Generator().manual_seed(seed)``, kept in frame order), uploaded once, so that K seeding passes do not upload
+    the data K times.  ``seed_frames`` defaults to ``min(N, 256 * n_clusters)`` for host frames: 256 frames per centre is a
+    stated choice, not a measurement (at K = 2000, d = 1024 it is 2 GB on the card); given explicitly it also samples a device
+    tensor.  Any other string raises.  Every iteration prepares the centres (``vq_prepare``), then per block, in block order, searches
     (``vq_search``: labels and squared error) and accumulates the centroid statistics, then updates the centres
     (``msmc_kmeans_update``; an empty centroid keeps its row -- it is not relocated) and reads back, once, the summed squared
     movement of the centres, the inertia (the search's squared error summed in float64), whether a label changed and the
@@ -139,10 +223,16 @@ def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, bl
         raise ValueError('block_frames must be positive')
     spans = [(s, min(N, s + block)) for s in range(0, N, block)]
 
-    if init is None:
+    init_indices = None
+    if isinstance(init, str):
+        if init != 'k-means++':
+            raise ValueError("init: the first centres [K, d], None or 'k-means++', got %r" % (init,))
+        centers, init_indices = _seed_plusplus(frames, N, K, seed, n_local_trials, seed_frames, device)
+    elif init is None:
         if not 1 <= K <= N:
             raise ValueError('n_clusters = %d: cannot draw that many distinct frames from %d' % (K, N))
         pick = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:K]
+        init_indices = pick.numpy()
         if torch.is_tensor(frames):
             centers = frames[pick.to(frames.device)]
         else:
@@ -198,4 +288,4 @@ def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, bl
             final, inertia = labels, history[-1]['inertia']
         hipvq._F32_OF['last'] = None            # (the search keeps its last block of frames for an EMA update that never comes)
         return KMeansFit(centers.cpu().numpy(), final.cpu().numpy(), inertia, n_iter, counts.cpu().numpy().astype(np.int64),
-                         step_labels.cpu().numpy(), history)
+                         step_labels.cpu().numpy(), history, init_indices)

@@ -40,6 +40,8 @@ _SIGNATURES = {
     'msmc_kmeans_stats_workspace': (_sz, [_i, _i, _i]),
     'msmc_kmeans_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     'msmc_kmeans_update': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    'msmc_kmeanspp_workspace': (_sz, [_i, _i, _i, _i]),
+    'msmc_kmeanspp_seed': (_i, [_vp, _i, _i, _i, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -44,7 +44,7 @@ import torch.nn.functional as F
 
 from ...hip import norm as hipnorm
 from ...hip import window as hipwindow
-from ...hip.kmeans import fit_kmeans  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
+from ...hip.kmeans import fit_kmeans, kmeans_plusplus  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
 from .modules import Quantize

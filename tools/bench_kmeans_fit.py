@@ -10,6 +10,10 @@ frames, d in {768, 1024}, K in {100, 500, 2000}.
   HBM bound   bytes the statistics must move -- one read of x plus 8 bytes of label per frame -- over the statistics time,
               against 8 TB/s (peak) and 6.3 TB/s (what a streaming read achieves on this chip)
 
+  seeding     (K >= 500) ``kmeans_plusplus`` (msmc_kmeanspp_seed) of the same frames: its two launches per step from the library's
+              event pairs, the pass over x against the bytes of x over a streaming read of x measured in the same run, the whole
+              seeding against one Lloyd iteration, and ``fit_kmeans(init='k-means++')`` against ``init=None`` after ``--fit-iters``
+
 Frames: K centres N(0, 1), a frame = a random centre + 0.5 N(0, 1); the centres searched are K frames.  Device events around
 each piece, two warm-up rounds, then ``--rounds`` timed rounds in which the pieces alternate; median / min.
 
@@ -57,7 +61,7 @@ def kernel_breakdown(fn):
     return out
 
 
-def one_shape(N, d, K, rounds):
+def blob_frames(N, d, K):
     gen = torch.Generator(device=dev).manual_seed(d + K)
     true = torch.randn(K, d, device=dev, generator=gen)
     x = torch.empty(N, d, device=dev)
@@ -65,6 +69,56 @@ def one_shape(N, d, K, rounds):
         n = min(N, s + (1 << 16)) - s
         which = torch.randint(0, K, (n,), device=dev, generator=gen)
         x[s:s + n] = true[which] + 0.5 * torch.randn(n, d, device=dev, generator=gen)
+    return x, gen
+
+
+def seeding(N, d, K, rounds, fit_iters):
+    """k-means++ seeding (msmc_kmeanspp_seed) of the same blob frames: a step against the bytes of x over the rate of a plain
+    streaming read of x measured here, the whole seeding against one Lloyd iteration, and the fit it starts against the fit from
+    K frames drawn uniformly"""
+    x, _ = blob_frames(N, d, K)
+    L = kmeans.default_local_trials(K)
+    with torch.no_grad():
+        read = [event_us(lambda: x.view(-1).sum(dtype=torch.float32)) for _ in range(2 + rounds)][2:]
+        stream = 4.0 * N * d / statistics.median(read) / 1e6                  # TB/s
+        few = 1 + 16                                        # centre 0 and sixteen steps: the launches one by one
+        kmeans.kmeans_plusplus(x, few, seed=1, n_local_trials=L)
+        torch.cuda.synchronize()
+        state = {}
+
+        def short():
+            state['out'] = kmeans.kmeans_plusplus(x, few, seed=1, n_local_trials=L)
+
+        parts = kernel_breakdown(short)
+        dist = (parts['kpp_dist_kernel'] - 0.0) / few       # (centre 0 is a pass with one candidate: counted as a step)
+        select = parts['kpp_select_kernel'] / few
+        whole = [event_us(lambda: state.update(out=kmeans.kmeans_plusplus(x, K, seed=1, n_local_trials=L))) for _ in range(1 + min(rounds, 3))][1:]
+        med = statistics.median(whole)
+        byts = 4.0 * N * d
+        print('d = %d, K = %d, N = %d, %d candidates per step: streaming read of x (torch sum) %.2f TB/s' % (d, K, N, L, stream))
+        print('  per step: kpp_dist_kernel %.1f us, kpp_select_kernel %.1f us (means over %d launches); %.1f MB of x -> the pass reads at '
+              '%.2f TB/s; bytes / measured streaming rate = %.1f us, bytes / 6.3 TB/s = %.1f us' % (
+                  dist, select, few, byts / 1e6, byts / dist / 1e6, byts / stream / 1e6, byts / STREAM_BYTES * 1e6))
+        print('  whole seeding: %.1f / %.1f ms (median / min of %d) = %.1f us per centre' % (med / 1e3, min(whole) / 1e3, len(whole), med / K))
+        potential = state['out'][2].cpu()
+        print('  seeding potential: %.6g after centre 0, %.6g after centre %d' % (float(potential[0]), float(potential[-1]), K - 1))
+        fits = {}
+        for name, init in (('uniform draw', None), ('k-means++', 'k-means++')):
+            rec = []
+            t = event_us(lambda: fits.update({name: kmeans.fit_kmeans(x, K, max_iter=fit_iters, tol=0.0, seed=1, init=init,
+                                                                     callback=lambda it, r: rec.append(r))}))
+            f = fits[name]
+            print('  fit from %-13s %d iterations in %.1f ms (seeding included): inertia %.9g, %d empty centroids; inertia of the first E '
+                  'step %.9g' % (name + ':', f.n_iter_, t / 1e3, f.inertia_, int((f.counts_ == 0).sum()), rec[0]['inertia']), flush=True)
+            if init is None:                                # (the variance pass and the final search are in: an upper figure)
+                per_iter = t / f.n_iter_
+                print('  one Lloyd iteration: at most %.1f ms (that fit / its iterations) -> the whole seeding is %.1f of them' % (
+                    per_iter / 1e3, med / per_iter))
+    vq._F32_OF['last'] = None
+
+
+def one_shape(N, d, K, rounds):
+    x, gen = blob_frames(N, d, K)
     centers = x[torch.randperm(N, device=dev, generator=gen)[:K]].clone()
     block = kmeans.default_block_frames(d)
     spans = [(s, min(N, s + block)) for s in range(0, N, block)]
@@ -127,6 +181,8 @@ if __name__ == '__main__':
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--frames', type=int, default=1 << 20)
     ap.add_argument('--quick', action='store_true', help='d = 1024, K = 500 only')
+    ap.add_argument('--seeding', action='store_true', help='the k-means++ seeding section (d in {768, 1024}, K in {500, 2000}) only')
+    ap.add_argument('--fit-iters', type=int, default=10, help='Lloyd iterations of the two fits the seeding section compares')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'this tool measures on the GPU; there is nothing to measure without one'
     print(torch.cuda.get_device_name(0))
@@ -136,5 +192,9 @@ if __name__ == '__main__':
         print('shader clock: not read (%s)' % type(err).__name__)
     for d in ((1024,) if args.quick else WIDTHS):
         for K in ((500,) if args.quick else CLUSTERS):
-            one_shape(args.frames, d, K, args.rounds)
-            torch.cuda.empty_cache()
+            if not args.seeding:
+                one_shape(args.frames, d, K, args.rounds)
+                torch.cuda.empty_cache()
+            if K >= 500:
+                seeding(args.frames, d, K, args.rounds, args.fit_iters)
+                torch.cuda.empty_cache()

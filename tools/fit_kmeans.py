@@ -7,7 +7,8 @@ msmctts_amd/hip/kmeans.py), and writes the ``.npy`` of centres [K, d] that ``qua
 ``id_list``: one utterance per line, whitespace-separated attributes; ``pattern``: the feature path with ``{0}``, ``{1}`` ... for
 the attributes, as the dataset configurations write it (``.npy``, ``.pt``, headerless float32 ``.dat`` / ``.mgc`` / ``.ap`` through
 the readers of datasets/readers.py; ``--dimension`` for the formats that need it).  ``--frames M`` keeps a seeded subsample of
-M frames drawn without replacement from all utterances (0: every frame).  Prints the inertia, the number of empty centroids
+M frames drawn without replacement from all utterances (0: every frame).  ``--init k-means++`` seeds the first centres with
+greedy k-means++ on the card (``--local-trials`` candidates per step) in place of K frames drawn uniformly.  Prints the inertia, the number of empty centroids
 and the movement of the centres per iteration.
 """
 import argparse
@@ -67,6 +68,9 @@ def main(argv=None):
     ap.add_argument('--iters', type=int, default=100)
     ap.add_argument('--tol', type=float, default=1e-4)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--init', choices=('frames', 'k-means++'), default='frames',
+                    help='the first centres: K frames drawn uniformly, or k-means++ seeding on the card')
+    ap.add_argument('--local-trials', type=int, default=None, help='candidates per k-means++ step (default 2 + floor(ln K), at most 16)')
     ap.add_argument('--dimension', type=int, default=None)
     ap.add_argument('--block-frames', type=int, default=None)
     ap.add_argument('--device', default=None, help='default: the current GPU')
@@ -82,7 +86,8 @@ def main(argv=None):
         print('iteration %3d  inertia %.9g  empty centroids %d  movement %.4g' % (it, rec['inertia'], rec['empty'], rec['shift']), flush=True)
 
     fit = fit_kmeans(x, args.clusters, max_iter=args.iters, tol=args.tol, seed=args.seed, block_frames=args.block_frames,
-                     device=args.device, callback=report)
+                     device=args.device, callback=report, init=None if args.init == 'frames' else args.init,
+                     n_local_trials=args.local_trials)
     fit.save(args.output)
     print('%s: [%d, %d] after %d iterations, inertia %.9g, %d empty centroids' % (
         args.output, fit.cluster_centers_.shape[0], fit.cluster_centers_.shape[1], fit.n_iter_, fit.inertia_,
