@@ -42,9 +42,8 @@ class _Attention(torch.autograd.Function):
         out = torch.empty(B, T, H * HEAD, dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty(B * H, T, dtype=torch.float32, device=qkv.device)
         seed = seed_word(qkv.device) if p_drop > 0 else None
-        lib.check(getattr(lib.get(), fwd)(lib.ptr(qkv), lib.ptr(bias), lib.ptr(out), lib.ptr(lse), B, T, H, bias.shape[1],
-                                          float(scale), float(p_drop), lib.ptr(seed) if seed is not None else None, int(salt),
-                                          lib.stream(qkv)), fwd)
+        lib.call(fwd, lib.ptr(qkv), lib.ptr(bias), lib.ptr(out), lib.ptr(lse), B, T, H, bias.shape[1], float(scale),
+                 float(p_drop), lib.ptr(seed) if seed is not None else None, int(salt), lib.stream(qkv))
         ctx.save_for_backward(qkv, bias, out, lse)
         ctx.args = (H, float(scale), float(p_drop), int(salt))
         return out
@@ -61,9 +60,8 @@ class _Attention(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         dsum = torch.empty(B * H, T, dtype=torch.float32, device=qkv.device)
         seed = seed_word(qkv.device) if p_drop > 0 else None
-        lib.check(getattr(lib.get(), bwd)(lib.ptr(qkv), lib.ptr(bias), lib.ptr(out), lib.ptr(lse), lib.ptr(g), lib.ptr(dqkv),
-                                          lib.ptr(dsum), B, T, H, bias.shape[1], scale, p_drop,
-                                          lib.ptr(seed) if seed is not None else None, salt, lib.stream(qkv)), bwd)
+        lib.call(bwd, lib.ptr(qkv), lib.ptr(bias), lib.ptr(out), lib.ptr(lse), lib.ptr(g), lib.ptr(dqkv), lib.ptr(dsum), B, T, H,
+                 bias.shape[1], scale, p_drop, lib.ptr(seed) if seed is not None else None, salt, lib.stream(qkv))
         return dqkv, None, None, None, None, None
 
 

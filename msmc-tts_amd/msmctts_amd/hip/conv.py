@@ -229,10 +229,10 @@ def _tune(kind, desc, launch, candidates):
 
 
 def _gather(desc, stream, what):
-    fn = lib.get().msmc_conv_gather
     if not getattr(desc, '_tuned', False):
+        fn = lib.get().msmc_conv_gather
         _tune('gather', desc, lambda: fn(ctypes.byref(desc), stream), _GATHER_CANDIDATES)
-    lib.check(fn(ctypes.byref(desc), stream), what)
+    lib.call('msmc_conv_gather', ctypes.byref(desc), stream, what=what)
 
 
 # -- deferred second stage of the no-atomics weight gradients ------------------------------------------------------------
@@ -282,7 +282,7 @@ class DeferredReduce(object):
         """the merged second stage of everything recorded since the last flush (on ``stream``: the caller has ordered it
         after the launches that wrote the partial results); the arena is free again afterwards"""
         if self.n:
-            lib.check(lib.get().msmc_conv_wgrad_reduce_pending(self.records, self.n, stream), 'msmc_conv_wgrad_reduce_pending')
+            lib.call('msmc_conv_wgrad_reduce_pending', self.records, self.n, stream)
         self.reset()
 
     def reset(self):
@@ -303,7 +303,7 @@ def _workspace(device, stream, nbytes):
     t = _WORKSPACES.get(key)
     if t is None or t.numel() * 4 < nbytes:
         grow = max(nbytes, 2 * (t.numel() * 4 if t is not None else 0), 8 << 20)
-        t = _WORKSPACES[key] = torch.empty((grow + 3) // 4, dtype=torch.float32, device=device)
+        t = _WORKSPACES[key] = lib.workspace(grow, device)
     return t.data_ptr(), t.numel() * 4
 
 
@@ -477,10 +477,10 @@ def const_gemm_split(x, wimg, cout):
     desc.x, desc.w, desc.out = x.data_ptr(), wimg.data_ptr(), out.data_ptr()
     desc.bias = desc.res = desc.res2 = desc.mask_src = None
     stream = lib.stream(x)
-    fn = lib.get().msmc_conv_gather
     if not getattr(desc, '_tuned', False):
+        fn = lib.get().msmc_conv_gather
         _tune('gather-split', desc, lambda: fn(ctypes.byref(desc), stream), _SPLIT_CANDIDATES)
-    lib.check(fn(ctypes.byref(desc), stream), 'msmc_conv_gather(split constant GEMM)')
+    lib.call('msmc_conv_gather', ctypes.byref(desc), stream, what='msmc_conv_gather(split constant GEMM)')
     return out
 
 
@@ -512,7 +512,7 @@ def const_gemm_split_group(xs, wimgs, couts):
         snaps.append(lib.ConvDesc.from_buffer_copy(desc))
         outs.append(out)
     arr = (lib.ConvDesc * len(snaps))(*snaps)
-    lib.check(lib.get().msmc_conv_gather_group(arr, len(snaps), stream), 'msmc_conv_gather_group(split constant GEMMs)')
+    lib.call('msmc_conv_gather_group', arr, len(snaps), stream, what='msmc_conv_gather_group(split constant GEMMs)')
     return outs
 
 
@@ -578,27 +578,25 @@ GROUP_PHASES = os.environ.get('MSMC_GROUP_PHASES', '1') != '0'            # stri
 
 def _gather_group(snaps, stream, what, device=None):
     """independent launches issued together (msmc_conv_gather_group) when that is the faster way for these shapes"""
-    L = lib.get()
-
     def single():
         for d in snaps:
-            lib.check(L.msmc_conv_gather(ctypes.byref(d), stream), what)
+            lib.call('msmc_conv_gather', ctypes.byref(d), stream, what=what)
 
     if len(snaps) == 1:
         return single()
     arr = (lib.ConvDesc * len(snaps))(*snaps)
 
     def grouped():
-        lib.check(L.msmc_conv_gather_group(arr, len(snaps), stream), what)
+        lib.call('msmc_conv_gather_group', arr, len(snaps), stream, what=what)
 
     def uniform(v):
         """launcher of the call with variant v on every member, None when the library refuses it for one of them"""
         forced = (lib.ConvDesc * len(snaps))(*[lib.ConvDesc.from_buffer_copy(d) for d in snaps])
         for d in forced:
             d.variant, d.split_shift = v, 0
-        if L.msmc_conv_gather_group(forced, len(snaps), stream) != 0:
+        if lib.get().msmc_conv_gather_group(forced, len(snaps), stream) != 0:      # (a refusal is an answer here, not an error)
             return None
-        return lambda: lib.check(L.msmc_conv_gather_group(forced, len(snaps), stream), what)
+        return lambda: lib.call('msmc_conv_gather_group', forced, len(snaps), stream, what=what)
 
     code, v = _group_choice('gather-group', snaps, grouped, single, uniform_fn=uniform)
     if code == 3:
@@ -813,18 +811,18 @@ def conv_wgrad_group(items):
                 wsp, wsb = keep
 
         def grouped():
-            lib.check(L.msmc_conv_wgrad_group_ws(arr, ga, dwa, dba, n, wsp, wsb, stream), 'msmc_conv_wgrad_group_ws')
+            lib.call('msmc_conv_wgrad_group_ws', arr, ga, dwa, dba, n, wsp, wsb, stream)
 
         def grouped4():
-            lib.check(L.msmc_conv_wgrad_group_ws4(arr, ga, dwa, dba, n, wsp, wsb, stream, 1), 'msmc_conv_wgrad_group_ws4')
+            lib.call('msmc_conv_wgrad_group_ws4', arr, ga, dwa, dba, n, wsp, wsb, stream, 1)
 
         g4 = grouped4 if sum(1 for d in part if d.variant >= 4) > 1 else None
 
         def single():
             off = 0                                   # (members get regions of their own: a deferred second stage reads
             for k in range(n):                        #  them all at the end of the backward pass)
-                lib.check(L.msmc_conv_wgrad_ws(ctypes.byref(part[k]), ga[k], dwa[k], dba[k],
-                                               (wsp + off) if needs[k] else None, needs[k], stream), 'msmc_conv_wgrad_ws')
+                lib.call('msmc_conv_wgrad_ws', ctypes.byref(part[k]), ga[k], dwa[k], dba[k], (wsp + off) if needs[k] else None,
+                         needs[k], stream)
                 off += needs[k]
 
         if n == 1:
@@ -869,14 +867,13 @@ def colsum(g2d, out=None):
     """g [rows, C] (fp32 / bf16) -> fp32 [C] column sums (bias gradient), added to ``out`` when given (no atomics: per-block
     partial sums + a fixed-order second stage, msmc_colsum_ws)."""
     rows, C = g2d.shape
-    L = lib.get()
     acc = out is not None
     if out is None:
         out = torch.empty(C, dtype=torch.float32, device=g2d.device)
-    need = int(L.msmc_colsum_workspace(rows, C))
-    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=g2d.device)
-    lib.check(L.msmc_colsum_ws(lib.ptr(g2d), lib.ptr(out, torch.float32), rows, C, _DT[g2d.dtype], int(acc), lib.ptr(ws), need,
-                               lib.stream(g2d)), 'msmc_colsum_ws')
+    need = int(lib.get().msmc_colsum_workspace(rows, C))
+    ws = lib.workspace(need, g2d.device)
+    lib.call('msmc_colsum_ws', lib.ptr(g2d), lib.ptr(out, torch.float32), rows, C, _DT[g2d.dtype], int(acc), lib.ptr(ws), need,
+             lib.stream(g2d))
     return out
 
 
@@ -886,9 +883,8 @@ def reflect_fold(gp, H, W, p=1, mask_src=None, slope=1.0):
     B, C = gp.shape[0], gp.shape[3]
     assert gp.shape[1:3] == (H + 2 * p, W + 2 * p) and gp.is_contiguous()
     gx = torch.empty((B, H, W, C), dtype=gp.dtype, device=gp.device)
-    lib.check(lib.get().msmc_reflect_fold(lib.ptr(gp), lib.ptr(mask_src) if mask_src is not None else None,
-                                          lib.ptr(gx), B, H, W, C, p, float(slope), _DT[gp.dtype], lib.stream(gp)),
-              'msmc_reflect_fold')
+    lib.call('msmc_reflect_fold', lib.ptr(gp), lib.ptr(mask_src) if mask_src is not None else None, lib.ptr(gx), B, H, W, C, p,
+             float(slope), _DT[gp.dtype], lib.stream(gp))
     return gx
 
 
@@ -896,15 +892,13 @@ def lrelu_bwd(g, y, slope):
     """g * (y > 0 ? 1 : slope) -- leaky-ReLU backward from the activation's output."""
     assert g.shape == y.shape and g.dtype == y.dtype and g.is_contiguous() and y.is_contiguous()
     gx = torch.empty_like(g)
-    lib.check(lib.get().msmc_lrelu_bwd(lib.ptr(g), lib.ptr(y), lib.ptr(gx), g.numel(), float(slope), _DT[g.dtype],
-                                       lib.stream(g)), 'msmc_lrelu_bwd')
+    lib.call('msmc_lrelu_bwd', lib.ptr(g), lib.ptr(y), lib.ptr(gx), g.numel(), float(slope), _DT[g.dtype], lib.stream(g))
     return gx
 
 
 def lrelu_bwd_group(pairs, slope):
     """[(g, y), ...] -> [g * (y > 0 ? 1 : slope), ...] in launches of up to six tensors (msmc_lrelu_bwd_multi)."""
     outs = []
-    L = lib.get()
     for i in range(0, len(pairs), 6):
         part = pairs[i:i + 6]
         n = len(part)
@@ -915,10 +909,9 @@ def lrelu_bwd_group(pairs, slope):
             _dev_ok(y)
             gxs.append(torch.empty_like(g))
         vp = ctypes.c_void_p * n
-        lib.check(L.msmc_lrelu_bwd_multi(vp(*[g.data_ptr() for g, _ in part]), vp(*[y.data_ptr() for _, y in part]),
-                                         vp(*[t.data_ptr() for t in gxs]), (ctypes.c_long * n)(*[g.numel() for g, _ in part]),
-                                         n, float(slope), _DT[part[0][0].dtype], lib.stream(part[0][0])),
-                  'msmc_lrelu_bwd_multi')
+        lib.call('msmc_lrelu_bwd_multi', vp(*[g.data_ptr() for g, _ in part]), vp(*[y.data_ptr() for _, y in part]),
+                 vp(*[t.data_ptr() for t in gxs]), (ctypes.c_long * n)(*[g.numel() for g, _ in part]), n, float(slope),
+                 _DT[part[0][0].dtype], lib.stream(part[0][0]))
         outs.extend(gxs)
     return outs
 
@@ -929,7 +922,6 @@ def reflect_fold_group(items, p=1, slope=1.0, tap_first=False):
     activated map and res the gradient of its other reader (msmc_reflect_fold_multi_tap)."""
     items = [tuple(it) + (None,) * (5 - len(it)) for it in items]
     outs = []
-    L = lib.get()
     for i in range(0, len(items), 6):
         part = items[i:i + 6]
         n = len(part)
@@ -946,12 +938,10 @@ def reflect_fold_group(items, p=1, slope=1.0, tap_first=False):
             masks.append(mask.data_ptr() if mask is not None else None)
             ress.append(res.data_ptr() if res is not None else None)
         vp, ip = ctypes.c_void_p * n, ctypes.c_int * n
-        entry = L.msmc_reflect_fold_multi_tap if tap_first else L.msmc_reflect_fold_multi_res
-        lib.check(entry(vp(*[t[0].data_ptr() for t in part]), vp(*masks), vp(*ress),
-                        vp(*[t.data_ptr() for t in gxs]), ip(*[t[0].shape[0] for t in part]),
-                        ip(*[t[1] for t in part]), ip(*[t[2] for t in part]),
-                        ip(*[t[0].shape[3] for t in part]), n, p, float(slope), _DT[part[0][0].dtype],
-                        lib.stream(part[0][0])), 'msmc_reflect_fold_multi_tap' if tap_first else 'msmc_reflect_fold_multi_res')
+        lib.call('msmc_reflect_fold_multi_tap' if tap_first else 'msmc_reflect_fold_multi_res',
+                 vp(*[t[0].data_ptr() for t in part]), vp(*masks), vp(*ress), vp(*[t.data_ptr() for t in gxs]),
+                 ip(*[t[0].shape[0] for t in part]), ip(*[t[1] for t in part]), ip(*[t[2] for t in part]),
+                 ip(*[t[0].shape[3] for t in part]), n, p, float(slope), _DT[part[0][0].dtype], lib.stream(part[0][0]))
         outs.extend(gxs)
     return outs
 

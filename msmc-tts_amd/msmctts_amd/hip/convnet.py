@@ -108,7 +108,7 @@ def own_streams(device, n, role):
     with torch.cuda.device(device):
         while len(have) < n:
             h = ctypes.c_void_p()
-            lib.check(lib.get().msmc_stream_create(ctypes.byref(h)), 'msmc_stream_create')
+            lib.call('msmc_stream_create', ctypes.byref(h))
             have.append(torch.cuda.ExternalStream(h.value, device=device))
     return have[:n]
 
@@ -274,9 +274,8 @@ def _wn_maps(items, device):
 def _wn_prepare(table, maps, n, blk, tblk, max_taps, stream, what):
     flat, o_norm, n_norm, o_tile = maps
     base = flat.data_ptr()
-    lib.check(lib.get().msmc_wn_prepare_multi_tiles(lib.ptr(table), n, blk, tblk, max_taps, ctypes.c_void_p(base),
-                                                    ctypes.c_void_p(base + 4 * o_norm), n_norm,
-                                                    ctypes.c_void_p(base + 4 * o_tile), stream), what)
+    lib.call('msmc_wn_prepare_multi_tiles', lib.ptr(table), n, blk, tblk, max_taps, ctypes.c_void_p(base),
+             ctypes.c_void_p(base + 4 * o_norm), n_norm, ctypes.c_void_p(base + 4 * o_tile), stream, what=what)
 
 
 class ConvBank(object):
@@ -617,9 +616,8 @@ class ConvBank(object):
                     for p, gview in self._grad_pairs(l):
                         if not live(p, gview):
                             gview.zero_()
-            lib.check(lib.get().msmc_wn_backward_multi_rows(lib.ptr(self.items_dev), len(self.layers), self.total_blocks,
-                                                            1 if accumulate else 0, self.max_row, lib.stream(self.w1)),
-                      'msmc_wn_backward_multi_rows')
+            lib.call('msmc_wn_backward_multi_rows', lib.ptr(self.items_dev), len(self.layers), self.total_blocks,
+                     1 if accumulate else 0, self.max_row, lib.stream(self.w1))
             for l in self.layers:
                 if l.index not in touched or not l.weight.requires_grad:
                     continue

@@ -16,11 +16,38 @@ from . import lib
 from . import vq as hipvq
 
 
+class _Frames(object):
+    """The frames [N, d] of a fit or a seeding -- a device tensor, a host tensor or a numpy array -- behind one way to read them:
+    ``rows`` and ``take`` return fp32, contiguous rows on ``device``: where a device tensor lies, else ``device`` (default: the
+    current GPU), uploaded by the call that asks for them"""
+
+    def __init__(self, frames, device=None):
+        if not torch.is_tensor(frames):
+            frames = np.asarray(frames)
+        if len(frames.shape) != 2:
+            raise ValueError('frames: expected [N, d], got %s' % (tuple(frames.shape),))
+        self.frames = frames
+        self.N, self.d = int(frames.shape[0]), int(frames.shape[1])
+        self.on_device = torch.is_tensor(frames) and frames.is_cuda
+        self.device = frames.device if self.on_device else torch.device('cuda' if device is None else device)
+
+    def _on_device(self, part):
+        if not torch.is_tensor(part):
+            part = torch.from_numpy(np.ascontiguousarray(part))
+        return part.detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+    def rows(self, s, e):
+        return self._on_device(self.frames[s:e])
+
+    def take(self, index):
+        """the rows whose frame numbers a CPU int64 tensor lists, in its order"""
+        if torch.is_tensor(self.frames):
+            return self._on_device(self.frames[index.to(self.frames.device)])
+        return self._on_device(self.frames[index.numpy()])
+
+
 def _workspace(N, d, K, device, workspace=None):
-    need = int(lib.get().msmc_kmeans_stats_workspace(N, d, K))
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-    return workspace
+    return lib.workspace(int(lib.get().msmc_kmeans_stats_workspace(N, d, K)), device, workspace)
 
 
 def centroid_stats(x, ind, K, out=None, accumulate=False, workspace=None):
@@ -42,10 +69,9 @@ def centroid_stats(x, ind, K, out=None, accumulate=False, workspace=None):
     if indc.numel() != N:
         raise ValueError('%d labels for %d frames' % (indc.numel(), N))
     workspace = _workspace(N, d, K, x.device, workspace)
-    lib.check(lib.get().msmc_kmeans_stats(lib.ptr(xc, torch.float32), lib.ptr(indc, torch.int64), lib.ptr(sums, torch.float32),
-                                          lib.ptr(counts, torch.float32), lib.ptr(workspace),
-                                          workspace.numel() * workspace.element_size(), N, d, K, int(bool(accumulate)),
-                                          lib.stream(xc)), 'msmc_kmeans_stats')
+    lib.call('msmc_kmeans_stats', lib.ptr(xc, torch.float32), lib.ptr(indc, torch.int64), lib.ptr(sums, torch.float32),
+             lib.ptr(counts, torch.float32), lib.ptr(workspace), workspace.numel() * workspace.element_size(), N, d, K,
+             int(bool(accumulate)), lib.stream(xc))
     return sums, counts
 
 
@@ -54,9 +80,8 @@ def centroid_update(sums, counts, centers):
     shift2 [K], the squared movement of every row (zero for an empty centroid)"""
     K, d = centers.shape
     shift2 = torch.empty((K,), dtype=torch.float32, device=centers.device)
-    lib.check(lib.get().msmc_kmeans_update(lib.ptr(sums, torch.float32), lib.ptr(counts, torch.float32),
-                                           lib.ptr(centers, torch.float32), lib.ptr(shift2), d, K, lib.stream(centers)),
-              'msmc_kmeans_update')
+    lib.call('msmc_kmeans_update', lib.ptr(sums, torch.float32), lib.ptr(counts, torch.float32), lib.ptr(centers, torch.float32),
+             lib.ptr(shift2), d, K, lib.stream(centers))
     return shift2
 
 
@@ -81,19 +106,12 @@ def kmeans_plusplus(frames, n_clusters, seed=0, n_local_trials=None, first=None,
     ``torch.Generator().manual_seed(seed)`` on the host.  A device tensor is seeded over all its frames where it lies; host
     frames are uploaded once, whole.  The whole seeding is enqueued without a read-back; every sum runs in a fixed order
     (include/msmc_hip.h), so the same inputs give the same bits."""
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(np.ascontiguousarray(np.asarray(frames), dtype=np.float32))
-    if frames.dim() != 2:
-        raise ValueError('frames: expected [N, d], got %s' % (tuple(frames.shape),))
-    N, d = int(frames.shape[0]), int(frames.shape[1])
+    frames = _Frames(frames, device)
+    N, d, device = frames.N, frames.d, frames.device
     K = int(n_clusters)
     if N < 1 or K < 1:
         raise ValueError('kmeans_plusplus needs at least one frame and one cluster (got N = %d, n_clusters = %d)' % (N, K))
     L = default_local_trials(K) if n_local_trials is None else int(n_local_trials)
-    if frames.is_cuda:
-        device = frames.device
-    else:
-        device = torch.device('cuda' if device is None else device)
     gen = torch.Generator().manual_seed(int(seed))
     drawn = int(torch.randint(N, (1,), generator=gen))
     first = drawn if first is None else int(first)
@@ -102,17 +120,15 @@ def kmeans_plusplus(frames, n_clusters, seed=0, n_local_trials=None, first=None,
     uniforms = torch.as_tensor(uniforms, dtype=torch.float64)
     if tuple(uniforms.shape) != (K - 1, L):
         raise ValueError('uniforms: expected [%d, %d], got %s' % (K - 1, L, tuple(uniforms.shape)))
-    x = frames.detach().to(device=device, dtype=torch.float32).contiguous()
+    x = frames.rows(0, N)
     u = uniforms.to(device).contiguous()
     centers = torch.empty((K, d), dtype=torch.float32, device=device)
     chosen = torch.empty((K,), dtype=torch.int64, device=device)
     potential = torch.empty((K,), dtype=torch.float64, device=device)
-    L_ = lib.get()
-    need = int(L_.msmc_kmeanspp_workspace(N, d, K, L))
-    workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
-    lib.check(L_.msmc_kmeanspp_seed(lib.ptr(x, torch.float32), N, d, K, L, first, lib.ptr(u, torch.float64),
-                                    lib.ptr(centers), lib.ptr(chosen), lib.ptr(potential), lib.ptr(workspace), need,
-                                    lib.stream(x)), 'msmc_kmeanspp_seed')
+    need = int(lib.get().msmc_kmeanspp_workspace(N, d, K, L))
+    workspace = lib.workspace(need, device)
+    lib.call('msmc_kmeanspp_seed', lib.ptr(x, torch.float32), N, d, K, L, first, lib.ptr(u, torch.float64), lib.ptr(centers),
+             lib.ptr(chosen), lib.ptr(potential), lib.ptr(workspace), need, lib.stream(x))
     return centers, chosen, potential
 
 
@@ -144,42 +160,33 @@ def default_block_frames(d):
     return max(1, ((1 << 31) - 1) // (4 * d))
 
 
-def _rows(frames, s, e, device):
-    xb = frames[s:e] if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames[s:e]))
-    return xb.detach().to(device=device, dtype=torch.float32).contiguous()
-
-
-def _mean_variance(frames, spans, device):
+def _mean_variance(frames, spans):
     """mean over the channels of the per-channel (population) variance of the frames, float64 sums over slabs of a block"""
-    N, d = frames.shape
-    s1 = torch.zeros(d, dtype=torch.float64, device=device)
-    s2 = torch.zeros(d, dtype=torch.float64, device=device)
+    s1 = torch.zeros(frames.d, dtype=torch.float64, device=frames.device)
+    s2 = torch.zeros(frames.d, dtype=torch.float64, device=frames.device)
     for s, e in spans:
-        for slab in _rows(frames, s, e, device).split(1 << 16):
+        for slab in frames.rows(s, e).split(1 << 16):
             v = slab.double()
             s1 += v.sum(0)
             s2 += (v * v).sum(0)
-    mean = s1 / N
-    return float((s2 / N - mean * mean).clamp_(min=0).mean())
+    mean = s1 / frames.N
+    return float((s2 / frames.N - mean * mean).clamp_(min=0).mean())
 
 
-def _seed_plusplus(frames, N, K, seed, n_local_trials, seed_frames, device):
+def _seed_plusplus(frames, K, seed, n_local_trials, seed_frames):
     """the first centres of ``fit_kmeans(init='k-means++')`` -> (centres [K, d] on the device, frame numbers [K] int64 numpy)"""
-    on_device = torch.is_tensor(frames) and frames.is_cuda
+    N = frames.N
     if seed_frames is None:
-        M = N if on_device else min(N, 256 * K)
+        M = N if frames.on_device else min(N, 256 * K)
     else:
         M = min(N, int(seed_frames))
         if M < 1:
             raise ValueError('seed_frames must be positive')
-    rows = None
+    rows, sample = None, frames.frames
     if M < N:
         rows = torch.sort(torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:M]).values
-        if torch.is_tensor(frames):
-            frames = frames[rows.to(frames.device)]
-        else:
-            frames = torch.from_numpy(np.ascontiguousarray(frames[rows.numpy()]))
-    centers, chosen, _ = kmeans_plusplus(frames, K, seed=seed, n_local_trials=n_local_trials, device=device)
+        sample = frames.take(rows)
+    centers, chosen, _ = kmeans_plusplus(sample, K, seed=seed, n_local_trials=n_local_trials, device=frames.device)
     chosen = chosen.cpu()
     return centers, (chosen if rows is None else rows[chosen]).numpy()
 
@@ -204,20 +211,13 @@ def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, bl
     number of empty centroids.  It stops when no label changed, when the movement is at most ``tol`` times the mean per-channel
     variance of the frames (scikit-learn's meaning of ``tol``), or after ``max_iter`` iterations.  Same inputs, same bits:
     every sum runs in a fixed order.  ``callback(iteration, record)`` is called with every ``history_`` record."""
-    if not torch.is_tensor(frames):
-        frames = np.asarray(frames)
-    if len(frames.shape) != 2:
-        raise ValueError('frames: expected [N, d], got %s' % (tuple(frames.shape),))
-    N, d = int(frames.shape[0]), int(frames.shape[1])
+    frames = _Frames(frames, device)
+    N, d, device = frames.N, frames.d, frames.device
     K = int(n_clusters)
     if max_iter < 1:
         raise ValueError('max_iter must be at least 1')
     if N < 1 or K < 1:
         raise ValueError('fit_kmeans needs at least one frame and one cluster (got N = %d, n_clusters = %d)' % (N, K))
-    if torch.is_tensor(frames) and frames.is_cuda:
-        device = frames.device
-    else:
-        device = torch.device('cuda' if device is None else device)
     block = default_block_frames(d) if block_frames is None else int(block_frames)
     if block < 1:
         raise ValueError('block_frames must be positive')
@@ -227,16 +227,13 @@ def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, bl
     if isinstance(init, str):
         if init != 'k-means++':
             raise ValueError("init: the first centres [K, d], None or 'k-means++', got %r" % (init,))
-        centers, init_indices = _seed_plusplus(frames, N, K, seed, n_local_trials, seed_frames, device)
+        centers, init_indices = _seed_plusplus(frames, K, seed, n_local_trials, seed_frames)
     elif init is None:
         if not 1 <= K <= N:
             raise ValueError('n_clusters = %d: cannot draw that many distinct frames from %d' % (K, N))
         pick = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:K]
         init_indices = pick.numpy()
-        if torch.is_tensor(frames):
-            centers = frames[pick.to(frames.device)]
-        else:
-            centers = torch.from_numpy(np.ascontiguousarray(frames[pick.numpy()]))
+        centers = frames.take(pick)
     else:
         centers = torch.as_tensor(np.asarray(init) if not torch.is_tensor(init) else init)
         if tuple(centers.shape) != (K, d):
@@ -244,7 +241,7 @@ def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, bl
     centers = centers.detach().to(device=device, dtype=torch.float32).contiguous().clone()
 
     with torch.no_grad():
-        limit = float(tol) * _mean_variance(frames, spans, device) if tol > 0 else 0.0
+        limit = float(tol) * _mean_variance(frames, spans) if tol > 0 else 0.0
         sums = torch.empty((K, d), dtype=torch.float32, device=device)
         counts = torch.empty((K,), dtype=torch.float32, device=device)
         workspace = _workspace(min(N, block), d, K, device)
@@ -255,7 +252,7 @@ def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, bl
         def e_step(embed_t, enorm, labels, stats):
             inertia = torch.zeros((), dtype=torch.float64, device=device)
             for b, (s, e) in enumerate(spans):
-                xb = _rows(frames, s, e, device)
+                xb = frames.rows(s, e)
                 _, diff, ind = hipvq.vq_search(xb, embed_t, enorm)
                 ind = ind.reshape(-1)
                 inertia += diff.sum(dtype=torch.float64)
@@ -286,6 +283,5 @@ def fit_kmeans(frames, n_clusters, max_iter=100, tol=1e-4, seed=0, init=None, bl
             inertia = float(e_step(*prepared(), final, False))
         else:                   # the same labels gave the same sums, hence the same centres, bit for bit: that search stands
             final, inertia = labels, history[-1]['inertia']
-        hipvq._F32_OF['last'] = None            # (the search keeps its last block of frames for an EMA update that never comes)
         return KMeansFit(centers.cpu().numpy(), final.cpu().numpy(), inertia, n_iter, counts.cpu().numpy().astype(np.int64),
                          step_labels.cpu().numpy(), history, init_indices)

@@ -2,6 +2,9 @@
 
 The library is built in-tree (``msmc-tts_amd/lib/libmsmc_hip.so``) by ``__graft_entry__.build()``.
 There is deliberately no fallback: a missing library, a failed launch or a host tensor raises.
+The modules of this package reach the ABI one way: ``call('msmc_x', ...)`` launches and raises on a non-zero return (``check``
+alone where the code has to look at the return code first), ``workspace`` allocates the scratch an ``msmc_*_workspace`` sized,
+``ptr`` / ``stream`` turn tensors into arguments.  Entry points that return a size or a count are called on ``get()`` directly.
 ``use_library_for_tests`` exists only so that the CPU test-suite can point the *same* Python ops at
 the kernel interpreter build (tests/emu); the product never calls it.
 """
@@ -310,3 +313,17 @@ def stream(t):
 def check(rc, what):
     if rc != 0:
         raise RuntimeError('%s failed with code %d' % (what, rc))
+
+
+def call(name, *args, what=None):
+    """Run the entry point ``name`` of the bound library and raise unless it returns 0.  The function is looked up on the handle
+    at every call: tools replace entry points there (``setattr(lib.get(), name, timed)``), and a cached one would miss them."""
+    check(getattr(get(), name)(*args), what or name)
+
+
+def workspace(nbytes, device, have=None, floor=0):
+    """Scratch of at least ``nbytes`` bytes: ``have`` itself where it is that large, else a new fp32 tensor of ``nbytes`` rounded
+    up to whole words and at least ``floor`` words"""
+    if have is not None and have.numel() * have.element_size() >= nbytes:
+        return have
+    return torch.empty(max(floor, (nbytes + 3) // 4), dtype=torch.float32, device=device)

@@ -50,8 +50,7 @@ class _L1Sum(torch.autograd.Function):
         out = torch.empty(1, dtype=torch.float32, device=a[0].device)
         tab = _table(a, b)
         part = torch.empty(lib.get().msmc_loss_multi_parts(), dtype=torch.float32, device=a[0].device)
-        lib.check(lib.get().msmc_l1_multi_fwd_ws(ctypes.byref(tab), lib.ptr(part), lib.ptr(out), lib.stream(out)),
-                  'msmc_l1_multi_fwd_ws')
+        lib.call('msmc_l1_multi_fwd_ws', ctypes.byref(tab), lib.ptr(part), lib.ptr(out), lib.stream(out))
         ctx.k = k
         ctx.save_for_backward(*tensors)
         return out.reshape(())
@@ -64,7 +63,7 @@ class _L1Sum(torch.autograd.Function):
         ga = [torch.empty_like(t) for t in a]          # preserve_format keeps the dense (permuted) strides
         tab = _table(a, b, ga)
         g = gout.reshape(1).float().contiguous()
-        lib.check(lib.get().msmc_l1_multi_bwd(ctypes.byref(tab), lib.ptr(g), lib.stream(g)), 'msmc_l1_multi_bwd')
+        lib.call('msmc_l1_multi_bwd', ctypes.byref(tab), lib.ptr(g), lib.stream(g))
         return (None,) + tuple(ga) + (None,) * k
 
 
@@ -75,8 +74,7 @@ class _MseConstSum(torch.autograd.Function):
         out = torch.empty(1, dtype=torch.float32, device=a[0].device)
         tab = _table(a)
         part = torch.empty(lib.get().msmc_loss_multi_parts(), dtype=torch.float32, device=a[0].device)
-        lib.check(lib.get().msmc_mse_const_multi_fwd_ws(ctypes.byref(tab), float(target), lib.ptr(part), lib.ptr(out),
-                                                        lib.stream(out)), 'msmc_mse_const_multi_fwd_ws')
+        lib.call('msmc_mse_const_multi_fwd_ws', ctypes.byref(tab), float(target), lib.ptr(part), lib.ptr(out), lib.stream(out))
         ctx.target = float(target)
         ctx.save_for_backward(*tensors)
         return out.reshape(())
@@ -87,8 +85,7 @@ class _MseConstSum(torch.autograd.Function):
         ga = [torch.empty_like(t) for t in a]
         tab = _table(a, None, ga)
         g = gout.reshape(1).float().contiguous()
-        lib.check(lib.get().msmc_mse_const_multi_bwd(ctypes.byref(tab), ctx.target, lib.ptr(g), lib.stream(g)),
-                  'msmc_mse_const_multi_bwd')
+        lib.call('msmc_mse_const_multi_bwd', ctypes.byref(tab), ctx.target, lib.ptr(g), lib.stream(g))
         return (None,) + tuple(ga)
 
 
@@ -107,8 +104,7 @@ class _MseConstHalves(torch.autograd.Function):
             out = torch.empty(1, dtype=torch.float32, device=tensors[0].device)
             ws = torch.empty(L.msmc_loss_multi_parts(), dtype=torch.float32, device=tensors[0].device)
             tab = _table(part)
-            lib.check(L.msmc_mse_const_multi_fwd_ws(ctypes.byref(tab), float(target), lib.ptr(ws), lib.ptr(out), lib.stream(out)),
-                      'msmc_mse_const_multi_fwd_ws')
+            lib.call('msmc_mse_const_multi_fwd_ws', ctypes.byref(tab), float(target), lib.ptr(ws), lib.ptr(out), lib.stream(out))
             outs.append(out.reshape(()))
         ctx.args = (B, float(c0), float(c1))
         ctx.save_for_backward(*tensors)
@@ -119,7 +115,6 @@ class _MseConstHalves(torch.autograd.Function):
         B, c0, c1 = ctx.args
         tensors = ctx.saved_tensors
         ga = [torch.empty_like(t) for t in tensors]
-        L = lib.get()
         for half, target, g in ((0, c0, g0), (1, c1, g1)):
             rows = (lambda t: t[:B]) if half == 0 else (lambda t: t[B:])
             if g is None:
@@ -128,7 +123,7 @@ class _MseConstHalves(torch.autograd.Function):
                 continue
             tab = _table([rows(t) for t in tensors], None, [rows(t) for t in ga])
             gs = g.reshape(1).float().contiguous()
-            lib.check(L.msmc_mse_const_multi_bwd(ctypes.byref(tab), target, lib.ptr(gs), lib.stream(gs)), 'msmc_mse_const_multi_bwd')
+            lib.call('msmc_mse_const_multi_bwd', ctypes.byref(tab), target, lib.ptr(gs), lib.stream(gs))
         return (None, None, None) + tuple(ga)
 
 
@@ -154,12 +149,10 @@ class _MaskedMean(torch.autograd.Function):
         assert b is None or (b.shape == a.shape and b.dtype in _DT and b.is_contiguous())
         assert lengths.dtype in (torch.int32, torch.int64) and lengths.is_contiguous() and lengths.numel() == a.shape[0]
         B, T, C = a.shape
-        L = lib.get()
-        part = torch.empty(L.msmc_masked_mean_parts(B), dtype=torch.float32, device=a.device)
+        part = torch.empty(lib.get().msmc_masked_mean_parts(B), dtype=torch.float32, device=a.device)
         out = torch.empty(2, dtype=torch.float32, device=a.device)
-        lib.check(L.msmc_masked_mean_fwd(lib.ptr(a), lib.ptr(b), lib.ptr(lengths), int(lengths.dtype == torch.int64), B, T, C,
-                                         _DT[a.dtype], _DT[b.dtype] if b is not None else 0, mode, lib.ptr(part), lib.ptr(out),
-                                         lib.stream(a)), 'msmc_masked_mean_fwd')
+        lib.call('msmc_masked_mean_fwd', lib.ptr(a), lib.ptr(b), lib.ptr(lengths), int(lengths.dtype == torch.int64), B, T, C,
+                 _DT[a.dtype], _DT[b.dtype] if b is not None else 0, mode, lib.ptr(part), lib.ptr(out), lib.stream(a))
         ctx.save_for_backward(a, b, lengths, out)
         ctx.mode = mode
         return out[0]
@@ -171,9 +164,9 @@ class _MaskedMean(torch.autograd.Function):
         ga = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         gb = torch.empty_like(b) if (b is not None and ctx.needs_input_grad[1]) else None
         g = gout.reshape(1).float().contiguous()
-        lib.check(lib.get().msmc_masked_mean_bwd(lib.ptr(a), lib.ptr(b), lib.ptr(lengths), int(lengths.dtype == torch.int64), B, T,
-                                                 C, _DT[a.dtype], _DT[b.dtype] if b is not None else 0, ctx.mode, lib.ptr(out),
-                                                 lib.ptr(g), lib.ptr(ga), lib.ptr(gb), lib.stream(a)), 'msmc_masked_mean_bwd')
+        lib.call('msmc_masked_mean_bwd', lib.ptr(a), lib.ptr(b), lib.ptr(lengths), int(lengths.dtype == torch.int64), B, T, C,
+                 _DT[a.dtype], _DT[b.dtype] if b is not None else 0, ctx.mode, lib.ptr(out), lib.ptr(g), lib.ptr(ga), lib.ptr(gb),
+                 lib.stream(a))
         return ga, gb, None, None
 
 
@@ -207,9 +200,9 @@ class _TripleLoss(torch.autograd.Function):
         args = (lib.ptr(p, torch.float32), lib.ptr(trg, torch.int64), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
                 lib.ptr(lossh), lib.ptr(gp), N, D, H, K, float(margin), int(mean))
         if chunk is None and triple_resident(D // H, K):
-            lib.check(lib.get().msmc_triple_loss(*args, lib.stream(p)), 'msmc_triple_loss')
+            lib.call('msmc_triple_loss', *args, lib.stream(p))
         else:
-            lib.check(lib.get().msmc_triple_loss_stream(*args, int(chunk or 0), lib.stream(p)), 'msmc_triple_loss_stream')
+            lib.call('msmc_triple_loss_stream', *args, int(chunk or 0), lib.stream(p))
         ctx.save_for_backward(gp)
         ctx.heads = H
         return lossh
@@ -244,8 +237,8 @@ class _WeightedSum(torch.autograd.Function):
         ts = [t.reshape(1) if t.dtype == torch.float32 else t.float().reshape(1) for t in terms]
         out = torch.empty(1, dtype=torch.float32, device=ts[0].device)
         vp, fp = ctypes.c_void_p * n, ctypes.c_float * n
-        lib.check(lib.get().msmc_scalar_wsum_fwd(vp(*[lib.ptr(t, torch.float32).value for t in ts]), fp(*weights), n, lib.ptr(out),
-                                                 lib.stream(out)), 'msmc_scalar_wsum_fwd')
+        lib.call('msmc_scalar_wsum_fwd', vp(*[lib.ptr(t, torch.float32).value for t in ts]), fp(*weights), n, lib.ptr(out),
+                 lib.stream(out))
         ctx.weights = tuple(weights)
         return out.reshape(())
 
@@ -254,8 +247,7 @@ class _WeightedSum(torch.autograd.Function):
         n = len(ctx.weights)
         g = gout.reshape(1).float().contiguous()
         gvec = torch.empty(n, dtype=torch.float32, device=g.device)
-        lib.check(lib.get().msmc_scalar_wsum_bwd(lib.ptr(g), (ctypes.c_float * n)(*ctx.weights), n, lib.ptr(gvec), lib.stream(g)),
-                  'msmc_scalar_wsum_bwd')
+        lib.call('msmc_scalar_wsum_bwd', lib.ptr(g), (ctypes.c_float * n)(*ctx.weights), n, lib.ptr(gvec), lib.stream(g))
         return (None,) + tuple(gvec[i] for i in range(n))
 
 

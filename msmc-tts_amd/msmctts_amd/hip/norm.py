@@ -61,16 +61,14 @@ class _AddLayerNorm(torch.autograd.Function):
             K = a.shape[-1]
             assert x.dtype == torch.bfloat16 and res is not None and a.is_contiguous() and a.dtype == x.dtype
             assert a.numel() == N * K and w.dtype == x.dtype and w.is_contiguous() and w.numel() == C * K
-            lib.check(lib.get().msmc_fc_add_ln_fwd(lib.ptr(a), lib.ptr(w), lib.ptr(bias, torch.float32), lib.ptr(res),
-                                                   lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32),
-                                                   lib.ptr(keep_row, torch.uint8), lib.ptr(y), lib.ptr(v), lib.ptr(mean),
-                                                   lib.ptr(rstd), N, C, K, float(eps), float(p_drop), lib.ptr(seed), salt,
-                                                   lib.stream(x)), 'msmc_fc_add_ln_fwd')
+            lib.call('msmc_fc_add_ln_fwd', lib.ptr(a), lib.ptr(w), lib.ptr(bias, torch.float32), lib.ptr(res),
+                     lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32), lib.ptr(keep_row, torch.uint8), lib.ptr(y),
+                     lib.ptr(v), lib.ptr(mean), lib.ptr(rstd), N, C, K, float(eps), float(p_drop), lib.ptr(seed), salt,
+                     lib.stream(x))
         else:
-            lib.check(lib.get().msmc_add_ln_fwd(lib.ptr(x), lib.ptr(res), lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32),
-                                                lib.ptr(keep_row, torch.uint8), lib.ptr(y), lib.ptr(v), lib.ptr(mean), lib.ptr(rstd),
-                                                N, C, float(eps), float(p_drop), lib.ptr(seed), salt, _DT[x.dtype], lib.stream(x)),
-                      'msmc_add_ln_fwd')
+            lib.call('msmc_add_ln_fwd', lib.ptr(x), lib.ptr(res), lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32),
+                     lib.ptr(keep_row, torch.uint8), lib.ptr(y), lib.ptr(v), lib.ptr(mean), lib.ptr(rstd), N, C, float(eps),
+                     float(p_drop), lib.ptr(seed), salt, _DT[x.dtype], lib.stream(x))
         ctx.save_for_backward(v, mean, rstd, gamma, keep_row)
         ctx.p_drop, ctx.salt, ctx.has_res = float(p_drop), salt, res is not None
         # leaf parameters: their gradients can leave in the pass's ONE parameter-gradient launch (_ln_flush) instead of a launch
@@ -84,7 +82,6 @@ class _AddLayerNorm(torch.autograd.Function):
         v, mean, rstd, gamma, keep_row = ctx.saved_tensors
         g = g.contiguous()
         N, C = _rows(v)
-        L = lib.get()
         gx = torch.empty_like(v)
         gres = torch.empty_like(v) if ctx.has_res else None
         # the parameter gradients: both accumulated into .grad by this pass and deferrable -> partial sums now, ONE reduction
@@ -101,13 +98,11 @@ class _AddLayerNorm(torch.autograd.Function):
         if not defer:
             dgamma = torch.empty(C, dtype=torch.float32, device=v.device)
             dbeta = torch.empty(C, dtype=torch.float32, device=v.device)
-        nbytes = int(L.msmc_add_ln_bwd_workspace(N, C))
-        ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=v.device)
+        ws = lib.workspace(int(lib.get().msmc_add_ln_bwd_workspace(N, C)), v.device, floor=1)
         seed = seed_word(v.device) if ctx.p_drop > 0 else None
-        lib.check(L.msmc_add_ln_bwd(lib.ptr(g), lib.ptr(v), lib.ptr(mean), lib.ptr(rstd), lib.ptr(gamma, torch.float32),
-                                    lib.ptr(keep_row, torch.uint8), lib.ptr(gx), lib.ptr(gres), lib.ptr(dgamma), lib.ptr(dbeta),
-                                    lib.ptr(ws), ws.numel() * 4, N, C, ctx.p_drop, lib.ptr(seed), ctx.salt, 0, _DT[v.dtype],
-                                    lib.stream(v)), 'msmc_add_ln_bwd')
+        lib.call('msmc_add_ln_bwd', lib.ptr(g), lib.ptr(v), lib.ptr(mean), lib.ptr(rstd), lib.ptr(gamma, torch.float32),
+                 lib.ptr(keep_row, torch.uint8), lib.ptr(gx), lib.ptr(gres), lib.ptr(dgamma), lib.ptr(dbeta), lib.ptr(ws),
+                 ws.numel() * 4, N, C, ctx.p_drop, lib.ptr(seed), ctx.salt, 0, _DT[v.dtype], lib.stream(v))
         if defer:
             _ln_queue(ws, (N + 15) // 16, C, ctx.params[0], ctx.params[1])
         return gx, gres, (dgamma if want_g else None), (dbeta if want_b else None), None, None, None, None, None
@@ -182,8 +177,7 @@ def _ln_flush():
                     slot.dgamma, slot.dbeta, slot.accumulate = targets[0][1].data_ptr(), targets[1][1].data_ptr(), 0
                 fresh.append(targets)
             dev = batch[0][0]
-            lib.check(lib.get().msmc_add_ln_param_multi(arr, len(batch), lib.stream(dev)),
-                      'msmc_add_ln_param_multi')
+            lib.call('msmc_add_ln_param_multi', arr, len(batch), lib.stream(dev))
             for targets in fresh:
                 for p, t, live in targets:
                     if not live:
@@ -214,8 +208,8 @@ def sum_n(tensors):
         return out
     out = torch.empty_like(a)
     ts = ts + [None] * (4 - len(ts))
-    lib.check(lib.get().msmc_sum_n(lib.ptr(ts[0]), lib.ptr(ts[1]), lib.ptr(ts[2]), lib.ptr(ts[3]), lib.ptr(out), a.numel(),
-                                   _DT[a.dtype], lib.stream(a)), 'msmc_sum_n')
+    lib.call('msmc_sum_n', lib.ptr(ts[0]), lib.ptr(ts[1]), lib.ptr(ts[2]), lib.ptr(ts[3]), lib.ptr(out), a.numel(), _DT[a.dtype],
+             lib.stream(a))
     return out
 
 
@@ -225,8 +219,8 @@ class _DropoutAdd(torch.autograd.Function):
         assert x.dtype in _DT and x.is_contiguous() and (res is None or (res.dtype == x.dtype and res.is_contiguous() and res.shape == x.shape))
         y = torch.empty_like(x)
         seed = seed_word(x.device) if p_drop > 0 else None
-        lib.check(lib.get().msmc_dropout_add_fwd(lib.ptr(x), lib.ptr(res), lib.ptr(y), x.numel(), float(p_drop), lib.ptr(seed), salt,
-                                                 _DT[x.dtype], lib.stream(x)), 'msmc_dropout_add_fwd')
+        lib.call('msmc_dropout_add_fwd', lib.ptr(x), lib.ptr(res), lib.ptr(y), x.numel(), float(p_drop), lib.ptr(seed), salt,
+                 _DT[x.dtype], lib.stream(x))
         ctx.p_drop, ctx.salt, ctx.has_res = float(p_drop), salt, res is not None
         ctx.set_materialize_grads(False)
         return y
@@ -239,8 +233,8 @@ class _DropoutAdd(torch.autograd.Function):
         gx = g
         if ctx.p_drop > 0 and ctx.needs_input_grad[0]:
             gx = torch.empty_like(g)
-            lib.check(lib.get().msmc_dropout_bwd(lib.ptr(g), lib.ptr(gx), g.numel(), ctx.p_drop, lib.ptr(seed_word(g.device)), ctx.salt,
-                                                 _DT[g.dtype], lib.stream(g)), 'msmc_dropout_bwd')
+            lib.call('msmc_dropout_bwd', lib.ptr(g), lib.ptr(gx), g.numel(), ctx.p_drop, lib.ptr(seed_word(g.device)), ctx.salt,
+                     _DT[g.dtype], lib.stream(g))
         return (gx if ctx.needs_input_grad[0] else None), (g if ctx.has_res else None), None, None
 
 
@@ -260,8 +254,8 @@ def row_mask(lengths, T, dtype):
     lengths = lengths.contiguous()
     B = lengths.numel()
     keep = torch.empty((B, T), dtype=dtype, device=lengths.device)
-    lib.check(lib.get().msmc_row_mask(lib.ptr(lengths, lengths.dtype), int(lengths.dtype == torch.int64), lib.ptr(keep), B, int(T),
-                                      _DT[dtype], lib.stream(lengths)), 'msmc_row_mask')
+    lib.call('msmc_row_mask', lib.ptr(lengths, lengths.dtype), int(lengths.dtype == torch.int64), lib.ptr(keep), B, int(T),
+             _DT[dtype], lib.stream(lengths))
     return keep
 
 
@@ -273,8 +267,7 @@ class _Gate(torch.autograd.Function):
         N = x.numel() // (2 * C)
         y = torch.empty(x.shape[:-1] + (C,), dtype=x.dtype, device=x.device)
         seed = seed_word(x.device) if p_drop > 0 else None
-        lib.check(lib.get().msmc_gate_fwd(lib.ptr(x), lib.ptr(y), N, C, float(p_drop), lib.ptr(seed), salt, _DT[x.dtype],
-                                          lib.stream(x)), 'msmc_gate_fwd')
+        lib.call('msmc_gate_fwd', lib.ptr(x), lib.ptr(y), N, C, float(p_drop), lib.ptr(seed), salt, _DT[x.dtype], lib.stream(x))
         ctx.save_for_backward(x)
         ctx.p_drop, ctx.salt = float(p_drop), salt
         return y
@@ -287,8 +280,8 @@ class _Gate(torch.autograd.Function):
         gx = torch.empty_like(x)
         g = g.contiguous()                       # (bound to a name: a temporary would be freed before the launch reads it)
         seed = seed_word(x.device) if ctx.p_drop > 0 else None
-        lib.check(lib.get().msmc_gate_bwd(lib.ptr(x), lib.ptr(g), lib.ptr(gx), N, C, ctx.p_drop, lib.ptr(seed),
-                                          ctx.salt, _DT[x.dtype], lib.stream(x)), 'msmc_gate_bwd')
+        lib.call('msmc_gate_bwd', lib.ptr(x), lib.ptr(g), lib.ptr(gx), N, C, ctx.p_drop, lib.ptr(seed), ctx.salt, _DT[x.dtype],
+                 lib.stream(x))
         return gx, None, None
 
 
@@ -306,10 +299,9 @@ class _FftPrologue(torch.autograd.Function):
         out = torch.empty((B, T, C), dtype=out_dtype, device=seq.device)
         keep_row = torch.empty(B * T, dtype=torch.uint8, device=seq.device)
         bias = torch.empty((B, Tp), dtype=torch.float32, device=seq.device) if Tp else None
-        lib.check(lib.get().msmc_fft_prologue(lib.ptr(seq), lib.ptr(lengths, lengths.dtype), int(lengths.dtype == torch.int64),
-                                              lib.ptr(table), table.shape[0], lib.ptr(out), lib.ptr(keep_row, torch.uint8),
-                                              lib.ptr(bias), B, T, C, int(Tp), _DT[seq.dtype], _DT[out_dtype],
-                                              lib.stream(seq)), 'msmc_fft_prologue')
+        lib.call('msmc_fft_prologue', lib.ptr(seq), lib.ptr(lengths, lengths.dtype), int(lengths.dtype == torch.int64),
+                 lib.ptr(table), table.shape[0], lib.ptr(out), lib.ptr(keep_row, torch.uint8), lib.ptr(bias), B, T, C, int(Tp),
+                 _DT[seq.dtype], _DT[out_dtype], lib.stream(seq))
         ctx.in_dtype = seq.dtype
         ctx.mark_non_differentiable(keep_row)
         ctx.set_materialize_grads(False)      # (the engine otherwise zero-fills a gradient for the mask and the bias: two launches)
@@ -337,7 +329,7 @@ class _Tanh(torch.autograd.Function):
     def forward(ctx, x):
         assert x.dtype in _DT and x.is_contiguous()
         y = torch.empty_like(x)
-        lib.check(lib.get().msmc_tanh_fwd(lib.ptr(x), lib.ptr(y), x.numel(), _DT[x.dtype], lib.stream(x)), 'msmc_tanh_fwd')
+        lib.call('msmc_tanh_fwd', lib.ptr(x), lib.ptr(y), x.numel(), _DT[x.dtype], lib.stream(x))
         ctx.save_for_backward(y)
         return y
 
@@ -346,8 +338,7 @@ class _Tanh(torch.autograd.Function):
         y, = ctx.saved_tensors
         gx = torch.empty_like(y)
         g = g.contiguous()
-        lib.check(lib.get().msmc_tanh_bwd(lib.ptr(y), lib.ptr(g), lib.ptr(gx), y.numel(), _DT[y.dtype],
-                                          lib.stream(y)), 'msmc_tanh_bwd')
+        lib.call('msmc_tanh_bwd', lib.ptr(y), lib.ptr(g), lib.ptr(gx), y.numel(), _DT[y.dtype], lib.stream(y))
         return gx
 
 
@@ -360,7 +351,7 @@ class _TanhF32(torch.autograd.Function):
     def forward(ctx, x):
         assert x.dtype in _DT and x.is_contiguous()
         y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        lib.check(lib.get().msmc_tanh_f32_fwd(lib.ptr(x), lib.ptr(y), x.numel(), _DT[x.dtype], lib.stream(x)), 'msmc_tanh_f32_fwd')
+        lib.call('msmc_tanh_f32_fwd', lib.ptr(x), lib.ptr(y), x.numel(), _DT[x.dtype], lib.stream(x))
         ctx.save_for_backward(y)
         ctx.dtype = x.dtype
         return y
@@ -370,8 +361,7 @@ class _TanhF32(torch.autograd.Function):
         y, = ctx.saved_tensors
         gx = torch.empty(y.shape, dtype=ctx.dtype, device=y.device)
         g = g.contiguous().float()
-        lib.check(lib.get().msmc_tanh_f32_bwd(lib.ptr(y), lib.ptr(g), lib.ptr(gx), y.numel(), _DT[ctx.dtype], lib.stream(y)),
-                  'msmc_tanh_f32_bwd')
+        lib.call('msmc_tanh_f32_bwd', lib.ptr(y), lib.ptr(g), lib.ptr(gx), y.numel(), _DT[ctx.dtype], lib.stream(y))
         return gx
 
 
@@ -386,10 +376,11 @@ def tanh_f32(x):
 # num_batches_tracked (checkpoint keys); the kernels update them on the device, so a captured step replays them.
 def _bn_workspace(bn, N, C, device):
     """scratch of the two-launch passes, kept on the module: both passes consume it before they return"""
-    nbytes = int(lib.get().msmc_bn_workspace(N, C))
-    ws = getattr(bn, '_hip_ws', None)
-    if ws is None or ws.device != device or ws.numel() * 4 < nbytes:
-        ws = bn._hip_ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
+    have = getattr(bn, '_hip_ws', None)
+    ws = lib.workspace(int(lib.get().msmc_bn_workspace(N, C)), device, have if have is not None and have.device == device else None,
+                       floor=1)
+    if ws is not have:
+        bn._hip_ws = ws
     return ws
 
 
@@ -398,7 +389,6 @@ class _BatchNorm(torch.autograd.Function):
     def forward(ctx, x, bn, out_fp32):
         assert x.dtype in _DT and x.is_contiguous()
         N, C = _rows(x)
-        L = lib.get()
         y = torch.empty(x.shape, dtype=torch.float32 if out_fp32 else x.dtype, device=x.device)
         rstd = torch.empty(C, dtype=torch.float32, device=x.device)
         ctx.training, ctx.bn, ctx.in_dtype = bn.training, bn, x.dtype
@@ -407,15 +397,13 @@ class _BatchNorm(torch.autograd.Function):
                 raise ValueError('Expected more than 1 value per channel when training, got input size %s' % (tuple(x.shape),))
             mean = torch.empty(C, dtype=torch.float32, device=x.device)
             ws = _bn_workspace(bn, N, C, x.device)
-            lib.check(L.msmc_bn_fwd(lib.ptr(x), lib.ptr(y), lib.ptr(mean), lib.ptr(rstd), lib.ptr(bn.running_mean, torch.float32),
-                                    lib.ptr(bn.running_var, torch.float32), lib.ptr(bn.num_batches_tracked, torch.int64),
-                                    lib.ptr(ws), ws.numel() * 4, N, C, float(bn.eps), float(bn.momentum), _DT[x.dtype],
-                                    _DT[y.dtype], lib.stream(x)), 'msmc_bn_fwd')
+            lib.call('msmc_bn_fwd', lib.ptr(x), lib.ptr(y), lib.ptr(mean), lib.ptr(rstd), lib.ptr(bn.running_mean, torch.float32),
+                     lib.ptr(bn.running_var, torch.float32), lib.ptr(bn.num_batches_tracked, torch.int64), lib.ptr(ws),
+                     ws.numel() * 4, N, C, float(bn.eps), float(bn.momentum), _DT[x.dtype], _DT[y.dtype], lib.stream(x))
             ctx.save_for_backward(x, mean, rstd)
         else:
-            lib.check(L.msmc_bn_eval_fwd(lib.ptr(x), lib.ptr(bn.running_mean, torch.float32), lib.ptr(bn.running_var, torch.float32),
-                                         lib.ptr(y), lib.ptr(rstd), N, C, float(bn.eps), _DT[x.dtype], _DT[y.dtype],
-                                         lib.stream(x)), 'msmc_bn_eval_fwd')
+            lib.call('msmc_bn_eval_fwd', lib.ptr(x), lib.ptr(bn.running_mean, torch.float32), lib.ptr(bn.running_var, torch.float32),
+                     lib.ptr(y), lib.ptr(rstd), N, C, float(bn.eps), _DT[x.dtype], _DT[y.dtype], lib.stream(x))
             ctx.save_for_backward(rstd)
         return y
 
@@ -424,18 +412,16 @@ class _BatchNorm(torch.autograd.Function):
         g = g.contiguous()
         if g.dtype != torch.float32 and g.dtype != ctx.in_dtype:
             g = g.to(ctx.in_dtype)
-        L = lib.get()
         gx = torch.empty(g.shape, dtype=ctx.in_dtype, device=g.device)
         N, C = _rows(g)
         if ctx.training:
             x, mean, rstd = ctx.saved_tensors
             ws = _bn_workspace(ctx.bn, N, C, g.device)
-            lib.check(L.msmc_bn_bwd(lib.ptr(g), lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(gx), lib.ptr(ws), ws.numel() * 4,
-                                    N, C, _DT[g.dtype], _DT[ctx.in_dtype], lib.stream(g)), 'msmc_bn_bwd')
+            lib.call('msmc_bn_bwd', lib.ptr(g), lib.ptr(x), lib.ptr(mean), lib.ptr(rstd), lib.ptr(gx), lib.ptr(ws), ws.numel() * 4, N, C,
+                     _DT[g.dtype], _DT[ctx.in_dtype], lib.stream(g))
         else:
             rstd, = ctx.saved_tensors
-            lib.check(L.msmc_bn_eval_bwd(lib.ptr(g), lib.ptr(rstd), lib.ptr(gx), N, C, _DT[g.dtype], _DT[ctx.in_dtype],
-                                         lib.stream(g)), 'msmc_bn_eval_bwd')
+            lib.call('msmc_bn_eval_bwd', lib.ptr(g), lib.ptr(rstd), lib.ptr(gx), N, C, _DT[g.dtype], _DT[ctx.in_dtype], lib.stream(g))
         return gx, None, None
 
 

@@ -29,8 +29,7 @@ class _Frames(torch.autograd.Function):
         B, L = x.shape
         xc = x.contiguous().float()
         fr = torch.empty((B, 1, T, NP), dtype=torch.float32, device=x.device)
-        lib.check(lib.get().msmc_stft_frames_fwd(lib.ptr(xc), lib.ptr(fr), B, L, T, n_fft, NP, hop, pad, lib.stream(xc)),
-                  'msmc_stft_frames_fwd')
+        lib.call('msmc_stft_frames_fwd', lib.ptr(xc), lib.ptr(fr), B, L, T, n_fft, NP, hop, pad, lib.stream(xc))
         ctx.args = (B, L, T, n_fft, NP, hop, pad)
         return fr
 
@@ -39,8 +38,7 @@ class _Frames(torch.autograd.Function):
         B, L, T, n_fft, NP, hop, pad = ctx.args
         g = g.contiguous()
         gx = torch.empty((B, L), dtype=torch.float32, device=g.device)
-        lib.check(lib.get().msmc_stft_frames_bwd(lib.ptr(g), lib.ptr(gx), B, L, T, n_fft, NP, hop, pad, lib.stream(g)),
-                  'msmc_stft_frames_bwd')
+        lib.call('msmc_stft_frames_bwd', lib.ptr(g), lib.ptr(gx), B, L, T, n_fft, NP, hop, pad, lib.stream(g))
         return gx, None, None, None, None, None
 
 
@@ -65,8 +63,7 @@ class _SpecMag(torch.autograd.Function):
         CP = spec.shape[-1]
         R = spec.numel() // CP
         mag = torch.empty(spec.shape[:-1] + (FP,), dtype=torch.float32, device=spec.device)
-        lib.check(lib.get().msmc_spec_mag_fwd(lib.ptr(spec), lib.ptr(mag), R, F, CP, FP, lo, clamp_mode, lib.stream(spec)),
-                  'msmc_spec_mag_fwd')
+        lib.call('msmc_spec_mag_fwd', lib.ptr(spec), lib.ptr(mag), R, F, CP, FP, lo, clamp_mode, lib.stream(spec))
         ctx.save_for_backward(spec, mag)
         ctx.args = (R, F, CP, FP, lo, clamp_mode)
         return mag
@@ -77,8 +74,8 @@ class _SpecMag(torch.autograd.Function):
         R, F, CP, FP, lo, clamp_mode = ctx.args
         g = g.contiguous()
         gs = torch.empty_like(spec)
-        lib.check(lib.get().msmc_spec_mag_bwd(lib.ptr(spec), lib.ptr(mag), lib.ptr(g), lib.ptr(gs), R, F, CP, FP, lo,
-                                              clamp_mode, lib.stream(g)), 'msmc_spec_mag_bwd')
+        lib.call('msmc_spec_mag_bwd', lib.ptr(spec), lib.ptr(mag), lib.ptr(g), lib.ptr(gs), R, F, CP, FP, lo, clamp_mode,
+                 lib.stream(g))
         return gs, None, None, None, None
 
 
@@ -97,19 +94,16 @@ def domain_channel(domain):
 
 def _image_fwd(mel, img, B, T, F, FP, channel, dtype, stream):
     if channel is None:
-        lib.check(lib.get().msmc_mrd_image_fwd_dt(lib.ptr(mel), lib.ptr(img), B, T, F, FP, _IMG_DT[dtype], stream), 'msmc_mrd_image_fwd_dt')
+        lib.call('msmc_mrd_image_fwd_dt', lib.ptr(mel), lib.ptr(img), B, T, F, FP, _IMG_DT[dtype], stream)
     else:
-        lib.check(lib.get().msmc_mrd_image1_fwd_dt(lib.ptr(mel), lib.ptr(img), B, T, F, FP, channel, _IMG_DT[dtype], stream),
-                  'msmc_mrd_image1_fwd_dt')
+        lib.call('msmc_mrd_image1_fwd_dt', lib.ptr(mel), lib.ptr(img), B, T, F, FP, channel, _IMG_DT[dtype], stream)
 
 
 def _image_bwd(mel, g, gm, B, T, F, FP, channel, dtype, stream):
     if channel is None:
-        lib.check(lib.get().msmc_mrd_image_bwd_dt(lib.ptr(mel), lib.ptr(g), lib.ptr(gm), B, T, F, FP, _IMG_DT[dtype], stream),
-                  'msmc_mrd_image_bwd_dt')
+        lib.call('msmc_mrd_image_bwd_dt', lib.ptr(mel), lib.ptr(g), lib.ptr(gm), B, T, F, FP, _IMG_DT[dtype], stream)
     else:
-        lib.check(lib.get().msmc_mrd_image1_bwd_dt(lib.ptr(mel), lib.ptr(g), lib.ptr(gm), B, T, F, FP, channel, _IMG_DT[dtype], stream),
-                  'msmc_mrd_image1_bwd_dt')
+        lib.call('msmc_mrd_image1_bwd_dt', lib.ptr(mel), lib.ptr(g), lib.ptr(gm), B, T, F, FP, channel, _IMG_DT[dtype], stream)
 
 
 class _MrdImage(torch.autograd.Function):
@@ -140,8 +134,7 @@ class _LogClamp(torch.autograd.Function):
     def forward(ctx, x, lo):
         xc = x.contiguous()
         y = torch.empty_like(xc)
-        lib.check(lib.get().msmc_log_clamp_fwd(lib.ptr(xc), lib.ptr(y), xc.numel(), lo, lib.stream(xc)),
-                  'msmc_log_clamp_fwd')
+        lib.call('msmc_log_clamp_fwd', lib.ptr(xc), lib.ptr(y), xc.numel(), lo, lib.stream(xc))
         ctx.save_for_backward(xc)
         ctx.lo = lo
         return y
@@ -151,8 +144,7 @@ class _LogClamp(torch.autograd.Function):
         (xc,) = ctx.saved_tensors
         g = g.contiguous()
         gx = torch.empty_like(xc)
-        lib.check(lib.get().msmc_log_clamp_bwd(lib.ptr(xc), lib.ptr(g), lib.ptr(gx), xc.numel(), ctx.lo, lib.stream(g)),
-                  'msmc_log_clamp_bwd')
+        lib.call('msmc_log_clamp_bwd', lib.ptr(xc), lib.ptr(g), lib.ptr(gx), xc.numel(), ctx.lo, lib.stream(g))
         return gx, None
 
 
@@ -245,17 +237,15 @@ class MrdFront(object):
         T = self.T = L // hop + 1
         lo, n_eff = dft[2], dft[3]
         self.frame_args = (T, n_eff, _pad4(n_eff), hop, n_fft // 2 - lo)
-        Lb = lib.get()
         xc = x.detach().contiguous().float()
         fr = torch.empty((B, 1, T, _pad4(n_eff)), dtype=torch.float32, device=x.device)
-        lib.check(Lb.msmc_stft_frames_fwd(lib.ptr(xc), lib.ptr(fr), B, L, T, n_eff, _pad4(n_eff), hop, n_fft // 2 - lo,
-                                          lib.stream(xc)), 'msmc_stft_frames_fwd')
+        lib.call('msmc_stft_frames_fwd', lib.ptr(xc), lib.ptr(fr), B, L, T, n_eff, _pad4(n_eff), hop, n_fft // 2 - lo,
+                 lib.stream(xc))
         geom = _geom1(T)
         self.spec = _const_gemm(fr, dft[0], geom, split)
         CP, FP = self.spec.shape[-1], _pad4(F)
         self.mag = torch.empty((B, 1, T, FP), dtype=torch.float32, device=x.device)
-        lib.check(Lb.msmc_spec_mag_fwd(lib.ptr(self.spec), lib.ptr(self.mag), B * T, F, CP, FP, 1e-7, 1, lib.stream(xc)),
-                  'msmc_spec_mag_fwd')
+        lib.call('msmc_spec_mag_fwd', lib.ptr(self.spec), lib.ptr(self.mag), B * T, F, CP, FP, 1e-7, 1, lib.stream(xc))
         self.mel = _const_gemm(self.mag, fb[0], geom, split) if fb is not None else self.mag
         self.img = torch.empty((B, F, T, 2 if self.channel is None else 1), dtype=dtype, device=x.device)
         _image_fwd(self.mel, self.img, B, T, F, FP, self.channel, dtype, lib.stream(xc))
@@ -270,7 +260,6 @@ class MrdFront(object):
         """gradient of the waveform rows r0 .. r1-1 from the gradient ``g`` of their image rows"""
         b, T, F = r1 - r0, self.T, self.F
         FP, CP = self.mag.shape[-1], self.spec.shape[-1]
-        Lb = lib.get()
         g = g.contiguous()
         if g.dtype != self.dtype:
             g = g.to(self.dtype)
@@ -281,13 +270,11 @@ class MrdFront(object):
         if self.fb is not None:
             gm = _const_gemm(gm, self.fb[1], geom, self.split, dgrad=True)
         gs = torch.empty_like(spec)
-        lib.check(Lb.msmc_spec_mag_bwd(lib.ptr(spec), lib.ptr(mag), lib.ptr(gm), lib.ptr(gs), b * T, F, CP, FP, 1e-7, 1,
-                                       lib.stream(g)), 'msmc_spec_mag_bwd')
+        lib.call('msmc_spec_mag_bwd', lib.ptr(spec), lib.ptr(mag), lib.ptr(gm), lib.ptr(gs), b * T, F, CP, FP, 1e-7, 1, lib.stream(g))
         gfr = _const_gemm(gs, self.dft[1], geom, self.split, dgrad=True)
         T_, n_eff, NP, hop, pad = self.frame_args
         gx = torch.empty((b, self.L), dtype=torch.float32, device=g.device)
-        lib.check(Lb.msmc_stft_frames_bwd(lib.ptr(gfr), lib.ptr(gx), b, self.L, T_, n_eff, NP, hop, pad, lib.stream(g)),
-                  'msmc_stft_frames_bwd')
+        lib.call('msmc_stft_frames_bwd', lib.ptr(gfr), lib.ptr(gx), b, self.L, T_, n_eff, NP, hop, pad, lib.stream(g))
         return gx
 
 
@@ -300,11 +287,10 @@ FRONTS_LOCKSTEP = _os.environ.get('MSMC_FRONTS_LOCKSTEP', '1') != '0'
 
 
 def _multi(ops):
-    L = lib.get()
     for i in range(0, len(ops), lib.SPECTRAL_MULTI_MAX):
         part = ops[i:i + lib.SPECTRAL_MULTI_MAX]
         arr = (lib.SpectralOp * len(part))(*part)
-        lib.check(L.msmc_spectral_multi(arr, len(part), part[0]._stream), 'msmc_spectral_multi')
+        lib.call('msmc_spectral_multi', arr, len(part), part[0]._stream)
 
 
 def _op(kind, stream, a, out, b=None, c=None, dtype=0, **kw):
@@ -540,7 +526,6 @@ class _LogMelPair(torch.autograd.Function):
     def backward(ctx, g, g_unused):
         spec, mag, m = ctx.saved_tensors
         B, L, T, n_eff, NP, hop, pad, F, FP, dft, mel, split, num_mels = ctx.args
-        Lb = lib.get()
         geom = _geom1(T)
         gfull = torch.zeros_like(m) if m.shape[-1] != num_mels else None
         if gfull is not None:
@@ -548,14 +533,14 @@ class _LogMelPair(torch.autograd.Function):
             g = gfull
         g = g.contiguous()
         gm = torch.empty_like(m)
-        lib.check(Lb.msmc_log_clamp_bwd(lib.ptr(m), lib.ptr(g), lib.ptr(gm), m.numel(), 1e-5, lib.stream(g)), 'msmc_log_clamp_bwd')
+        lib.call('msmc_log_clamp_bwd', lib.ptr(m), lib.ptr(g), lib.ptr(gm), m.numel(), 1e-5, lib.stream(g))
         gmag = _const_gemm(gm, mel[1], geom, split, dgrad=True)
         gs = torch.empty_like(spec)
-        lib.check(Lb.msmc_spec_mag_bwd(lib.ptr(spec), lib.ptr(mag), lib.ptr(gmag), lib.ptr(gs), B * T, F, spec.shape[-1], FP, 1e-9, 0,
-                                       lib.stream(g)), 'msmc_spec_mag_bwd')
+        lib.call('msmc_spec_mag_bwd', lib.ptr(spec), lib.ptr(mag), lib.ptr(gmag), lib.ptr(gs), B * T, F, spec.shape[-1], FP, 1e-9, 0,
+                 lib.stream(g))
         gfr = _const_gemm(gs, dft[1], geom, split, dgrad=True)
         gy = torch.empty((B, L), dtype=torch.float32, device=g.device)
-        lib.check(Lb.msmc_stft_frames_bwd(lib.ptr(gfr), lib.ptr(gy), B, L, T, n_eff, NP, hop, pad, lib.stream(g)), 'msmc_stft_frames_bwd')
+        lib.call('msmc_stft_frames_bwd', lib.ptr(gfr), lib.ptr(gy), B, L, T, n_eff, NP, hop, pad, lib.stream(g))
         return gy, None, None, None, None, None, None, None
 
 
@@ -578,8 +563,8 @@ class _WaveFan(torch.autograd.Function):
         n = len(copies)
         if n:
             vp, ip = ctypes.c_void_p * n, ctypes.c_int * n
-            lib.check(lib.get().msmc_wave_fan_fwd(lib.ptr(yc), vp(*[lib.ptr(c).value for c in copies]), ip(*padded), n, B, L,
-                                                  _IMG_DT[dtype], lib.stream(yc)), 'msmc_wave_fan_fwd')
+            lib.call('msmc_wave_fan_fwd', lib.ptr(yc), vp(*[lib.ptr(c).value for c in copies]), ip(*padded), n, B, L, _IMG_DT[dtype],
+                     lib.stream(yc))
         ctx.args = (B, L, int(n_alias), tuple(padded), dtype)
         return tuple(yc.view_as(yc) for _ in range(n_alias)) + tuple(copies)
 
@@ -595,8 +580,7 @@ class _WaveFan(torch.autograd.Function):
         vp32, vp16, ip = ctypes.c_void_p * max(1, n32), ctypes.c_void_p * max(1, n), ctypes.c_int * max(1, n)
         p32 = vp32(*([None if g is None else lib.ptr(g).value for g in g32] or [None]))
         p16 = vp16(*([None if g is None else lib.ptr(g).value for g in g16] or [None]))
-        lib.check(lib.get().msmc_wave_fan_bwd(p32, n32, p16, ip(*(list(padded) or [L])), n, lib.ptr(gy), B, L, _IMG_DT[dtype],
-                                              lib.stream(gy)), 'msmc_wave_fan_bwd')
+        lib.call('msmc_wave_fan_bwd', p32, n32, p16, ip(*(list(padded) or [L])), n, lib.ptr(gy), B, L, _IMG_DT[dtype], lib.stream(gy))
         return gy, None, None, None
 
 
@@ -613,6 +597,6 @@ def window_gather(starts, wav, nframes, hop):
     assert starts.dtype == torch.int64 and starts.numel() == B and wav.dtype == torch.float32 and wav.is_contiguous()
     frames = torch.empty((B, nframes), dtype=torch.int64, device=wav.device)
     target = torch.empty((B, nframes * hop), dtype=torch.float32, device=wav.device)
-    lib.check(lib.get().msmc_window_gather(lib.ptr(starts), lib.ptr(wav), lib.ptr(frames), lib.ptr(target), B, int(nframes), int(hop),
-                                           int(L), lib.stream(wav)), 'msmc_window_gather')
+    lib.call('msmc_window_gather', lib.ptr(starts), lib.ptr(wav), lib.ptr(frames), lib.ptr(target), B, int(nframes), int(hop), int(L),
+             lib.stream(wav))
     return frames, target

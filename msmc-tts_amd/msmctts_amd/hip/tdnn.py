@@ -16,9 +16,9 @@ _DT = {torch.float32: 0, torch.bfloat16: 1}
 
 def _workspace(holder, name, nbytes, device):
     """scratch of a multi-launch pass, kept on the module that owns the operator: consumed before the call returns"""
-    ws = getattr(holder, name, None)
-    if ws is None or ws.device != device or ws.numel() * 4 < nbytes:
-        ws = torch.empty(max(4, (nbytes + 3) // 4), dtype=torch.float32, device=device)
+    have = getattr(holder, name, None)
+    ws = lib.workspace(nbytes, device, have if have is not None and have.device == device else None, floor=4)
+    if ws is not have:
         setattr(holder, name, ws)
     return ws
 
@@ -62,17 +62,15 @@ class _ReluBatchNorm(torch.autograd.Function):
                 raise ValueError('Expected more than 1 value per channel when training, got input size %s' % (tuple(x.shape),))
             mean = torch.empty(C, dtype=torch.float32, device=x.device)
             ws = _workspace(bn, '_hip_ws', int(L.msmc_relu_bn_workspace(N, C)), x.device)
-            lib.check(L.msmc_relu_bn_fwd(_raw(x), ldx, lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32), lib.ptr(y), C,
-                                         lib.ptr(mean), lib.ptr(rstd), lib.ptr(bn.running_mean, torch.float32),
-                                         lib.ptr(bn.running_var, torch.float32), lib.ptr(bn.num_batches_tracked, torch.int64),
-                                         lib.ptr(ws), ws.numel() * 4, N, C, float(bn.eps), float(bn.momentum), _DT[x.dtype],
-                                         lib.stream(x)), 'msmc_relu_bn_fwd')
+            lib.call('msmc_relu_bn_fwd', _raw(x), ldx, lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32), lib.ptr(y), C,
+                     lib.ptr(mean), lib.ptr(rstd), lib.ptr(bn.running_mean, torch.float32), lib.ptr(bn.running_var, torch.float32),
+                     lib.ptr(bn.num_batches_tracked, torch.int64), lib.ptr(ws), ws.numel() * 4, N, C, float(bn.eps),
+                     float(bn.momentum), _DT[x.dtype], lib.stream(x))
             ctx.save_for_backward(x, gamma, mean, rstd)
         else:
-            lib.check(L.msmc_relu_bn_eval_fwd(_raw(x), ldx, lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32),
-                                              lib.ptr(bn.running_mean, torch.float32), lib.ptr(bn.running_var, torch.float32),
-                                              lib.ptr(y), C, lib.ptr(rstd), N, C, float(bn.eps), _DT[x.dtype], lib.stream(x)),
-                      'msmc_relu_bn_eval_fwd')
+            lib.call('msmc_relu_bn_eval_fwd', _raw(x), ldx, lib.ptr(gamma, torch.float32), lib.ptr(beta, torch.float32),
+                     lib.ptr(bn.running_mean, torch.float32), lib.ptr(bn.running_var, torch.float32), lib.ptr(y), C, lib.ptr(rstd),
+                     N, C, float(bn.eps), _DT[x.dtype], lib.stream(x))
             # (the running mean as it was in the forward pass: a later training step may move the buffer)
             ctx.save_for_backward(x, gamma, bn.running_mean.clone() if any(ctx.needs_input_grad) else bn.running_mean, rstd)
         return y
@@ -88,9 +86,9 @@ class _ReluBatchNorm(torch.autograd.Function):
         gx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
         ws = _workspace(ctx.bn, '_hip_ws', int(L.msmc_relu_bn_workspace(N, C)), x.device)
-        fn, what = (L.msmc_relu_bn_bwd, 'msmc_relu_bn_bwd') if ctx.training else (L.msmc_relu_bn_eval_bwd, 'msmc_relu_bn_eval_bwd')
-        lib.check(fn(lib.ptr(g), C, _raw(x), ldx, lib.ptr(mean), lib.ptr(rstd), lib.ptr(gamma), lib.ptr(gx), C, lib.ptr(dgamma),
-                     lib.ptr(dbeta), lib.ptr(ws), ws.numel() * 4, N, C, _DT[x.dtype], lib.stream(x)), what)
+        lib.call('msmc_relu_bn_bwd' if ctx.training else 'msmc_relu_bn_eval_bwd', lib.ptr(g), C, _raw(x), ldx, lib.ptr(mean),
+                 lib.ptr(rstd), lib.ptr(gamma), lib.ptr(gx), C, lib.ptr(dgamma), lib.ptr(dbeta), lib.ptr(ws), ws.numel() * 4, N, C,
+                 _DT[x.dtype], lib.stream(x))
         return gx, dgamma, dbeta, None
 
 
@@ -130,9 +128,9 @@ class _SEResidual(torch.autograd.Function):
         mean = torch.empty(B, C, dtype=torch.float32, device=x.device)
         hidden = torch.empty(B, C // 2, dtype=torch.float32, device=x.device)
         ws = _workspace(holder, '_hip_ws', int(L.msmc_se_workspace(B, T, C)), x.device)
-        lib.check(L.msmc_se_fwd(lib.ptr(x), lib.ptr(res, x.dtype), lib.ptr(W1, torch.float32), lib.ptr(b1, torch.float32),
-                                lib.ptr(W2, torch.float32), lib.ptr(b2, torch.float32), lib.ptr(y), lib.ptr(gate), lib.ptr(mean),
-                                lib.ptr(hidden), lib.ptr(ws), ws.numel() * 4, B, T, C, _DT[x.dtype], lib.stream(x)), 'msmc_se_fwd')
+        lib.call('msmc_se_fwd', lib.ptr(x), lib.ptr(res, x.dtype), lib.ptr(W1, torch.float32), lib.ptr(b1, torch.float32),
+                 lib.ptr(W2, torch.float32), lib.ptr(b2, torch.float32), lib.ptr(y), lib.ptr(gate), lib.ptr(mean), lib.ptr(hidden),
+                 lib.ptr(ws), ws.numel() * 4, B, T, C, _DT[x.dtype], lib.stream(x))
         ctx.save_for_backward(x, W1, W2, gate, mean, hidden)
         ctx.holder = holder
         return y
@@ -147,15 +145,14 @@ class _SEResidual(torch.autograd.Function):
         L = lib.get()
         dgate = torch.empty_like(gate)
         ws = _workspace(ctx.holder, '_hip_ws', int(L.msmc_se_workspace(B, T, C)), x.device)
-        lib.check(L.msmc_se_bwd_gate(lib.ptr(g), lib.ptr(x), lib.ptr(dgate), lib.ptr(ws), ws.numel() * 4, B, T, C, _DT[x.dtype],
-                                     lib.stream(x)), 'msmc_se_bwd_gate')
+        lib.call('msmc_se_bwd_gate', lib.ptr(g), lib.ptr(x), lib.ptr(dgate), lib.ptr(ws), ws.numel() * 4, B, T, C, _DT[x.dtype],
+                 lib.stream(x))
         # the two small layers, on [B, C] / [B, C/2] quantities (a few KB: stock matrix products)
         dz2 = dgate * gate * (1.0 - gate)
         dz1 = (dz2 @ W2) * (hidden > 0).to(dz2.dtype)
         dmean = ((dz1 @ W1) / T).contiguous()
         gx = torch.empty_like(x)
-        lib.check(L.msmc_se_bwd_apply(lib.ptr(g), lib.ptr(gate), lib.ptr(dmean), lib.ptr(gx), B, T, C, _DT[x.dtype], lib.stream(x)),
-                  'msmc_se_bwd_apply')
+        lib.call('msmc_se_bwd_apply', lib.ptr(g), lib.ptr(gate), lib.ptr(dmean), lib.ptr(gx), B, T, C, _DT[x.dtype], lib.stream(x))
         return gx, g, dz1.t() @ mean, dz1.sum(0), dz2.t() @ hidden, dz2.sum(0), None
 
 
@@ -189,8 +186,8 @@ class _AttentiveStatsPool(torch.autograd.Function):
         out = torch.empty(B, 2 * C, dtype=torch.float32, device=x.device)
         stats = torch.empty(B, 4, C, dtype=torch.float32, device=x.device)
         ws = _workspace(holder, '_hip_ws', int(L.msmc_asp_workspace(B, T, C)), x.device)
-        lib.check(L.msmc_asp_fwd(lib.ptr(x), lib.ptr(a, x.dtype), lib.ptr(out), lib.ptr(stats), lib.ptr(ws), ws.numel() * 4, B, T, C,
-                                 _DT[x.dtype], lib.stream(x)), 'msmc_asp_fwd')
+        lib.call('msmc_asp_fwd', lib.ptr(x), lib.ptr(a, x.dtype), lib.ptr(out), lib.ptr(stats), lib.ptr(ws), ws.numel() * 4, B, T, C,
+                 _DT[x.dtype], lib.stream(x))
         ctx.save_for_backward(x, a, stats)
         return out
 
@@ -200,8 +197,8 @@ class _AttentiveStatsPool(torch.autograd.Function):
         B, T, C = x.shape
         g = g.contiguous().float()
         gx, ga = torch.empty_like(x), torch.empty_like(a)
-        lib.check(lib.get().msmc_asp_bwd(lib.ptr(g), lib.ptr(x), lib.ptr(a), lib.ptr(stats), lib.ptr(gx), lib.ptr(ga), B, T, C,
-                                         _DT[x.dtype], lib.stream(x)), 'msmc_asp_bwd')
+        lib.call('msmc_asp_bwd', lib.ptr(g), lib.ptr(x), lib.ptr(a), lib.ptr(stats), lib.ptr(gx), lib.ptr(ga), B, T, C, _DT[x.dtype],
+                 lib.stream(x))
         return gx, ga, None
 
 

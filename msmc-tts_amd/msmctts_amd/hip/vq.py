@@ -29,15 +29,12 @@ def vq_prepare(embed, frames=None):
     H, d, K = embed.shape
     embed_t = torch.empty((H, K, d), dtype=torch.float32, device=embed.device)
     enorm = torch.empty((H, K), dtype=torch.float32, device=embed.device)
-    L = lib.get()
-    lib.check(L.msmc_vq_prepare(lib.ptr(embed, torch.float32), lib.ptr(embed_t), lib.ptr(enorm), H, d, K,
-                                lib.stream(embed)), 'msmc_vq_prepare')
+    lib.call('msmc_vq_prepare', lib.ptr(embed, torch.float32), lib.ptr(embed_t), lib.ptr(enorm), H, d, K, lib.stream(embed))
     wanted = SHORTLIST and (frames is None or frames * K >= SHORTLIST_MIN_WORK)
-    nbytes = int(L.msmc_vq_shortlist_bytes(H, d, K)) if wanted else 0
+    nbytes = int(lib.get().msmc_vq_shortlist_bytes(H, d, K)) if wanted else 0
     if nbytes:
         image = torch.empty(nbytes, dtype=torch.uint8, device=embed.device)
-        lib.check(L.msmc_vq_prepare_shortlist(lib.ptr(embed_t), lib.ptr(enorm), lib.ptr(image), H, d, K,
-                                              lib.stream(embed)), 'msmc_vq_prepare_shortlist')
+        lib.call('msmc_vq_prepare_shortlist', lib.ptr(embed_t), lib.ptr(enorm), lib.ptr(image), H, d, K, lib.stream(embed))
         embed_t.shortlist_image = image
     return embed_t, enorm
 
@@ -64,9 +61,9 @@ def wide_takes(H, d, K):
     return H == 1 and d % 16 == 0 and 16 <= d <= 2048 and K >= 1
 
 
-def _search_wide(L, xc, embed_t, enorm, quant, diff, ind, N, d, K):
-    return L.msmc_vq_search_wide(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32), lib.ptr(quant),
-                                 lib.ptr(diff), lib.ptr(ind), N, d, K, lib.stream(xc))
+def _search_wide(xc, embed_t, enorm, quant, diff, ind, N, d, K):
+    lib.call('msmc_vq_search_wide', lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32), lib.ptr(quant),
+             lib.ptr(diff), lib.ptr(ind), N, d, K, lib.stream(xc))
 
 
 class _VQSearch(torch.autograd.Function):
@@ -76,32 +73,31 @@ class _VQSearch(torch.autograd.Function):
         D = H * d
         assert x.shape[-1] == D, (x.shape, embed_t.shape)
         xc = x.contiguous().float()
-        _F32_OF['last'] = (x.data_ptr(), x.dtype, tuple(x.shape), xc)      # (the EMA update of the same frames reads this copy)
+        # the EMA update of the same frames reads the copy a cast made; fp32 frames are their own copy and are not kept alive
+        _F32_OF['last'] = (x.data_ptr(), x.dtype, tuple(x.shape), xc) if x.dtype != torch.float32 else None
         N = xc.numel() // D
         quant = torch.empty_like(xc)
         diff = torch.empty(xc.shape[:-1] + (d,), dtype=torch.float32, device=x.device)
         ind = torch.empty(xc.shape[:-1] + (H,), dtype=torch.int64, device=x.device)
-        L = lib.get()
         if wide:
             if H != 1:
                 raise RuntimeError('msmc_vq_search_wide takes one head (got %d)' % H)
-            lib.check(_search_wide(L, xc, embed_t, enorm, quant, diff, ind, N, d, K), 'msmc_vq_search_wide')
+            _search_wide(xc, embed_t, enorm, quant, diff, ind, N, d, K)
         elif stream_chunk is not None:
-            lib.check(L.msmc_vq_search_stream(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
-                                              lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, int(stream_chunk),
-                                              lib.stream(xc)), 'msmc_vq_search_stream')
+            lib.call('msmc_vq_search_stream', lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
+                     lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, int(stream_chunk), lib.stream(xc))
         elif image is not None and (force_shortlist or N * K >= SHORTLIST_MIN_WORK):
-            lib.check(L.msmc_vq_search_shortlist(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
-                                                 lib.ptr(image, torch.uint8), lib.ptr(quant), lib.ptr(diff), lib.ptr(ind),
-                                                 lib.ptr(SLOW_COUNT, torch.int64), N, D, H, K, lib.stream(xc)),
-                      'msmc_vq_search_shortlist')
+            lib.call('msmc_vq_search_shortlist', lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
+                     lib.ptr(image, torch.uint8), lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), lib.ptr(SLOW_COUNT, torch.int64),
+                     N, D, H, K, lib.stream(xc))
         else:
-            rc = L.msmc_vq_search(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
-                                  lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, lib.stream(xc))
+            # (the return code decides before it is checked: the raw call)
+            rc = lib.get().msmc_vq_search(lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
+                                          lib.ptr(quant), lib.ptr(diff), lib.ptr(ind), N, D, H, K, lib.stream(xc))
             if rc == E_SHAPE and wide_takes(H, d, K):
                 # a single head msmc_vq_search refuses (it launched nothing): K % 16 != 0, or a d beyond what the streamed
                 # launcher fits -- the GEMM-shaped kernel of csrc/vq_wide.inc
-                lib.check(_search_wide(L, xc, embed_t, enorm, quant, diff, ind, N, d, K), 'msmc_vq_search_wide')
+                _search_wide(xc, embed_t, enorm, quant, diff, ind, N, d, K)
             else:
                 lib.check(rc, 'msmc_vq_search')
         ctx.save_for_backward(xc, quant)
@@ -123,9 +119,8 @@ class _VQSearch(torch.autograd.Function):
         g_quant = g_quant.contiguous().float()
         g_diff = None if g_diff is None else g_diff.contiguous().float()
         gx = torch.empty_like(xc)
-        L = lib.get()
-        lib.check(L.msmc_vq_backward(lib.ptr(g_quant), lib.ptr(g_diff), lib.ptr(xc), lib.ptr(quant), lib.ptr(gx),
-                                     N, D, ctx.heads, lib.stream(xc)), 'msmc_vq_backward')
+        lib.call('msmc_vq_backward', lib.ptr(g_quant), lib.ptr(g_diff), lib.ptr(xc), lib.ptr(quant), lib.ptr(gx), N, D, ctx.heads,
+                 lib.stream(xc))
         return gx.to(ctx.in_dtype), None, None, None, None, None, None
 
 
@@ -192,18 +187,13 @@ def vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, wo
 def _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace=None):
     B, T, D = x.shape
     H, d, K = embed.shape
-    L = lib.get()
-    need = int(L.msmc_vq_ema_workspace(B * T, D, H, K))
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+    workspace = lib.workspace(int(lib.get().msmc_vq_ema_workspace(B * T, D, H, K)), x.device, workspace)
     xc = _f32_frames(x.detach())
     indc = ind.contiguous()                 # (named: a temporary would be released before the launch reads it)
     length = length.to(device=x.device, dtype=torch.int64).contiguous()
-    lib.check(L.msmc_vq_ema_update(lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length),
-                                   lib.ptr(embed, torch.float32), lib.ptr(cluster_size, torch.float32),
-                                   lib.ptr(embed_avg, torch.float32), lib.ptr(workspace),
-                                   workspace.numel() * workspace.element_size(), B, T, D, H, K, float(decay),
-                                   float(eps), lib.stream(xc)), 'msmc_vq_ema_update')
+    lib.call('msmc_vq_ema_update', lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(embed, torch.float32),
+             lib.ptr(cluster_size, torch.float32), lib.ptr(embed_avg, torch.float32), lib.ptr(workspace),
+             workspace.numel() * workspace.element_size(), B, T, D, H, K, float(decay), float(eps), lib.stream(xc))
     return workspace
 
 
@@ -224,23 +214,18 @@ class CodebookSync(object):
     def collect(self, x, ind, length):
         B, T, D = x.shape
         H, d, K = self.embed.shape
-        L = lib.get()
-        need = int(L.msmc_vq_ema_workspace(B * T, D, H, K))
-        if self.workspace is None or self.workspace.numel() * 4 < need:
-            self.workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+        self.workspace = lib.workspace(int(lib.get().msmc_vq_ema_workspace(B * T, D, H, K)), x.device, self.workspace)
         xc = x.detach().contiguous().float()
         indc = ind.contiguous()
         length = length.to(device=x.device, dtype=torch.int64).contiguous()
-        lib.check(L.msmc_vq_ema_stats(lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(self.stats),
-                                      lib.ptr(self.workspace), self.workspace.numel() * 4, B, T, D, H, K, lib.stream(xc)),
-                  'msmc_vq_ema_stats')
+        lib.call('msmc_vq_ema_stats', lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(self.stats),
+                 lib.ptr(self.workspace), self.workspace.numel() * 4, B, T, D, H, K, lib.stream(xc))
 
     def apply(self):
         H, d, K = self.embed.shape
-        lib.check(lib.get().msmc_vq_ema_apply(lib.ptr(self.stats), lib.ptr(self.embed, torch.float32),
-                                              lib.ptr(self.cluster_size, torch.float32), lib.ptr(self.embed_avg, torch.float32),
-                                              H * d, H, K, float(self.decay), float(self.eps), lib.stream(self.stats)),
-                  'msmc_vq_ema_apply')
+        lib.call('msmc_vq_ema_apply', lib.ptr(self.stats), lib.ptr(self.embed, torch.float32),
+                 lib.ptr(self.cluster_size, torch.float32), lib.ptr(self.embed_avg, torch.float32), H * d, H, K,
+                 float(self.decay), float(self.eps), lib.stream(self.stats))
 
 
 _FLAT = {}            # (device, elements) -> persistent exchange buffer of flush_codebook_sync

@@ -37,8 +37,8 @@ class _WindowGather(torch.autograd.Function):
         B, T, C = x.shape
         n = win.shape[0]
         out = torch.empty((n, max(W, 0), C), dtype=out_dtype, device=x.device)
-        lib.check(lib.get().msmc_window_gather_fwd(lib.ptr(x), _DT[x.dtype], lib.ptr(win), lib.ptr(out), _DT[out_dtype], B, T, C, n,
-                                                   W, lib.stream(x)), 'msmc_window_gather_fwd')
+        lib.call('msmc_window_gather_fwd', lib.ptr(x), _DT[x.dtype], lib.ptr(win), lib.ptr(out), _DT[out_dtype], B, T, C, n, W,
+                 lib.stream(x))
         ctx.save_for_backward(win)
         ctx.args = (B, T, C, W, x.dtype)
         return out
@@ -51,8 +51,8 @@ class _WindowGather(torch.autograd.Function):
         if g.dtype not in _DT:
             g = g.float()
         gx = torch.empty((B, T, C), dtype=dtype, device=g.device)
-        lib.check(lib.get().msmc_window_gather_bwd(lib.ptr(g), _DT[g.dtype], lib.ptr(win), lib.ptr(gx), _DT[dtype], B, T, C,
-                                                   win.shape[0], W, lib.stream(g)), 'msmc_window_gather_bwd')
+        lib.call('msmc_window_gather_bwd', lib.ptr(g), _DT[g.dtype], lib.ptr(win), lib.ptr(gx), _DT[dtype], B, T, C, win.shape[0],
+                 W, lib.stream(g))
         return gx, None, None, None
 
 

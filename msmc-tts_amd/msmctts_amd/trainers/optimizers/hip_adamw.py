@@ -135,10 +135,9 @@ class HipAdamW(Optimizer):
             if not torch.is_tensor(lr):
                 lr = group['lr'] = torch.tensor(float(lr), dtype=torch.float32, device=ps[0].device)
             b1, b2 = group['betas']
-            lib.check(lib.get().msmc_opt_clip_adamw(lib.ptr(table), nt, blocks, float(max_norm or 0.0), lib.ptr(partial),
-                                                    lib.ptr(flat['norm_coef']), lib.ptr(lr.reshape(1)), lib.ptr(flat['step']),
-                                                    float(b1), float(b2), float(group['eps']), float(group['weight_decay']), 1,
-                                                    lib.stream(partial)), 'msmc_opt_clip_adamw')
+            lib.call('msmc_opt_clip_adamw', lib.ptr(table), nt, blocks, float(max_norm or 0.0), lib.ptr(partial),
+                     lib.ptr(flat['norm_coef']), lib.ptr(lr.reshape(1)), lib.ptr(flat['step']), float(b1), float(b2),
+                     float(group['eps']), float(group['weight_decay']), 1, lib.stream(partial))
             self.grad_norm = flat['norm_coef'][0]
             convnet.params_updated(self._owners.setdefault(id(group), _Owner()), ps)    # (raw-pointer update: no version counter moves)
         return loss
