@@ -607,6 +607,21 @@ int msmc_triple_loss(const float* p, const int64_t* trg, const float* embed_t, c
 int msmc_triple_loss_stream(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp,
                             int N, int D, int H, int K, float margin, int mean, int chunk, msmc_stream stream);
 
+/* The same loss for ONE wide head, GEMM-shaped (msmc-tts_amd/csrc/triple_wide.inc): the k-means unit codebooks (d = 768 / 1024,
+ * K = 100 .. 2000) neither kernel above takes.  Operands and outputs as msmc_triple_loss with H = 1 (embed_t [K][d] / enorm [K]
+ * from msmc_vq_prepare, lossh [N], gp [N][d]).  Two launches on fp32 MFMA: the K products p.e_k of a frame tile, the hinge
+ * decisions, lossh and a bit mask of the active codewords (the workspace: 8 bytes per frame and 64 codewords,
+ * msmc_triple_loss_wide_workspace, 0 for N <= 0 or a shape the kernel refuses); then mask x embed_t per (frame tile, 128
+ * channels).  The target's own row never enters the gradient.  The active t_k + margin are added before the one
+ * multiplication by 1 / d (1 / (d K) for the mean); the gradient rows add up per 64 codewords, those sums in a compensated
+ * sum.  The order of every fp32 sum depends on (d, K) alone -- not on N or the grid; no atomics.  Takes d % 16 == 0,
+ * 16 <= d <= 2048, K >= 1; MSMC_E_SHAPE otherwise or for p / embed_t / gp not 16-byte aligned, nothing launched; 0 at once,
+ * with no launch, for N == 0; MSMC_E_WORKSPACE for a workspace below msmc_triple_loss_wide_workspace. */
+size_t msmc_triple_loss_wide_workspace(int N, int d, int K);
+int msmc_triple_loss_wide(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp,
+                          int N, int d, int K, float margin, int mean, void* workspace, size_t workspace_bytes,
+                          msmc_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * E1/V3  fused element-wise / row-normalisation kernels of the FFT blocks and the quantiser glue (csrc/norm.hip).
  * Replace the stock-kernel chains behind

@@ -25,6 +25,10 @@ void msmc_vq_set_variant(int v);
 /* Tests / sweeps: waves that share a 16-frame tile in msmc_vq_search_wide, 1 / 2 / 4 (0, the default: chosen from N). */
 void msmc_vq_wide_set_split(int wc);
 
+/* Tests / sweeps: frames per workgroup of both launches of msmc_triple_loss_wide, 16 / 32 / 64 (0, the default: chosen from N);
+ * the results do not depend on it, bit for bit. */
+void msmc_triple_wide_set_frames(int ft);
+
 /* Tests / sweeps: workgroups of the persistent grid of msmc_conv_gather variant 32 (0 = one or two per CU). */
 void msmc_conv_set_gather4_grid(int n);
 /* 1: the variant-32 members of msmc_conv_gather_group share ONE persistent grid (interpreter-tested, not yet timed on the
@@ -53,7 +57,7 @@ void msmc_conv_set_wgrad4_ablate(int mask);
 /* ---- observers (read-only: nothing here changes what a product call computes or launches) ---- */
 /* Symbol of the search kernel the calling thread's most recent msmc_vq_search launched (profiling aid). */
 const char* msmc_vq_last_kernel(void);
-/* Symbol of the kernel the calling thread's most recent triple-loss call launched, resident or streamed (profiling aid). */
+/* Symbol of the kernel the calling thread's most recent triple-loss call launched, resident, streamed or wide (its first launch) (profiling aid). */
 const char* msmc_loss_last_kernel(void);
 /* Per-launch profiling log (process-wide; bench.py's kernel table): while enabled, every kernel this library launches
  * -- from any thread: the backward pass runs on the autograd engine's -- is bracketed by a HIP event pair recorded on the launch's own stream and logged under the

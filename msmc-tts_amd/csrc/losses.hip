@@ -402,11 +402,12 @@ __global__ __launch_bounds__(256) void triple_loss_kernel(const float* __restric
     }
 }
 
-// symbol of the triple-loss kernel the calling thread's most recent msmc_triple_loss / msmc_triple_loss_stream launched
+// symbol of the triple-loss kernel the calling thread's most recent msmc_triple_loss / _stream / _wide launched
 static thread_local const char* msmc_loss_last = "";
 extern "C" const char* msmc_loss_last_kernel(void) { return msmc_loss_last; }
 
 #include "triple_stream.inc"
+#include "triple_wide.inc"
 
 extern "C" {
 int msmc_triple_loss(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp, int N,
@@ -441,6 +442,14 @@ int msmc_triple_loss_stream(const float* p, const int64_t* trg, const float* emb
     if (!p || !trg || !embed_t || !enorm || !lossh || !gp || N < 0 || H <= 0 || K <= 0 || D <= 0 || D % H) return MSMC_E_SHAPE;
     if (((size_t)p | (size_t)embed_t | (size_t)gp) & 15) return MSMC_E_SHAPE;
     return triple_stream_launch(p, trg, embed_t, enorm, lossh, gp, N, D, H, K, margin, mean, chunk, stream);
+}
+size_t msmc_triple_loss_wide_workspace(int N, int d, int K) { return (N > 0 && trw_takes(d, K)) ? trw_workspace_bytes(N, K) : 0; }
+int msmc_triple_loss_wide(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp,
+                          int N, int d, int K, float margin, int mean, void* workspace, size_t workspace_bytes,
+                          msmc_stream stream) {
+    if (!p || !trg || !embed_t || !enorm || !lossh || !gp) return MSMC_E_SHAPE;
+    if (((size_t)p | (size_t)embed_t | (size_t)gp) & 15) return MSMC_E_SHAPE;
+    return triple_wide_launch(p, trg, embed_t, enorm, lossh, gp, N, d, K, margin, mean, workspace, workspace_bytes, stream);
 }
 int msmc_masked_mean_parts(int B) { return B * MM_BX; }
 int msmc_masked_mean_fwd(const void* a, const void* b, const void* lengths, int len_is_64, int B, int T, int C, int a_dtype,

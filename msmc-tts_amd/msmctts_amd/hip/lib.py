@@ -130,6 +130,8 @@ _SIGNATURES.update({
     'msmc_mse_const_multi_bwd': (_i, [ctypes.POINTER(TensorTable), _f, _vp, _vp]),
     'msmc_triple_loss': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     'msmc_triple_loss_stream': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp]),
+    'msmc_triple_loss_wide_workspace': (_sz, [_i, _i, _i]),
+    'msmc_triple_loss_wide': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     'msmc_masked_mean_parts': (_i, [_i]),
     'msmc_masked_mean_fwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'msmc_masked_mean_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -226,6 +228,7 @@ _DEBUG_SIGNATURES = {
     'msmc_vq_set_shortlist_ablate': (None, [_i]),
     'msmc_vq_set_variant': (None, [_i]),
     'msmc_vq_wide_set_split': (None, [_i]),
+    'msmc_triple_wide_set_frames': (None, [_i]),
     'msmc_conv_set_grouping': (None, [_i]),
     'msmc_conv_set_pipeline': (None, [_i]),
     'msmc_conv_set_wgrad_split': (None, [_i]),

@@ -190,16 +190,27 @@ def triple_kernel_takes(d, K):
     return d in STREAM_DIMS and K >= 1
 
 
+def triple_wide_takes(H, d, K):
+    """the shapes ``msmc_triple_loss_wide`` (csrc/triple_wide.inc) takes: one head, d % 16 == 0, 16 <= d <= 2048, any K >= 1"""
+    return H == 1 and d % 16 == 0 and 16 <= d <= 2048 and K >= 1
+
+
 class _TripleLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, p, trg, embed_t, enorm, margin, mean, chunk):
+    def forward(ctx, p, trg, embed_t, enorm, margin, mean, chunk, wide=False):
         N, D = p.shape
         H, K = enorm.shape
         lossh = torch.empty(N, H, dtype=torch.float32, device=p.device)
         gp = torch.empty(N, D, dtype=torch.float32, device=p.device)
         args = (lib.ptr(p, torch.float32), lib.ptr(trg, torch.int64), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32),
                 lib.ptr(lossh), lib.ptr(gp), N, D, H, K, float(margin), int(mean))
-        if chunk is None and triple_resident(D // H, K):
+        if wide or (chunk is None and not triple_kernel_takes(D // H, K) and triple_wide_takes(H, D // H, K)):
+            if H != 1:
+                raise RuntimeError('msmc_triple_loss_wide takes one head (got %d)' % H)
+            ws = lib.workspace(int(lib.get().msmc_triple_loss_wide_workspace(N, D, K)), p.device)
+            lib.call('msmc_triple_loss_wide', *args[:7], D, K, float(margin), int(mean), lib.ptr(ws),
+                     ws.numel() * ws.element_size(), lib.stream(p))
+        elif chunk is None and triple_resident(D // H, K):
             lib.call('msmc_triple_loss', *args, lib.stream(p))
         else:
             lib.call('msmc_triple_loss_stream', *args, int(chunk or 0), lib.stream(p))
@@ -213,16 +224,18 @@ class _TripleLoss(torch.autograd.Function):
         N, D = gp.shape
         H = ctx.heads
         g = glossh.reshape(N, H, 1).to(gp.dtype)
-        return (gp.view(N, H, D // H) * g).view(N, D), None, None, None, None, None, None
+        return (gp.view(N, H, D // H) * g).view(N, D), None, None, None, None, None, None, None
 
 
-def triple_loss(p, trg, embed_t, enorm, reduction='sum', margin=1e-6, chunk=None):
+def triple_loss(p, trg, embed_t, enorm, reduction='sum', margin=1e-6, chunk=None, wide=False):
     """per-(frame, head) triple loss of predictions ``p`` [N, D] against target indices ``trg`` [N, H] and the prepared codebook
     (``hip/vq.py vq_prepare``: embed_t [H, K, d], enorm [H, K]) in one launch -> [N, H].  ``chunk=None``: msmc_triple_loss where a
     head's codebook fits LDS, else msmc_triple_loss_stream with the launcher's chunk; an int forces the streamed entry with that
-    chunk of codewords (0 = the launcher's choice)."""
+    chunk of codewords (0 = the launcher's choice).  A single head at a width neither of them takes (d = 768 / 1024: the k-means
+    unit codebooks) runs msmc_triple_loss_wide (csrc/triple_wide.inc, two launches) where that kernel takes it; ``wide=True`` =
+    that entry whatever the shape (tests and tools: its summation order differs from the other kernels')."""
     return _TripleLoss.apply(p.contiguous().float(), trg.contiguous().long(), embed_t, enorm, float(margin), reduction == 'mean',
-                             chunk)
+                             chunk, bool(wide))
 
 
 def usable(*tensors):

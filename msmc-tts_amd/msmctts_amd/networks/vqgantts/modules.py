@@ -80,13 +80,16 @@ class Quantize(nn.Module):
     def compute_triple_loss(self, prd_quant, trg_quant, reduction='mean', margin=1e-6, adaptive_margin=False):
         """hinge of (squared distance to the target codeword) against the squared distance to every codeword (reference
         modules.py:86-116, the 'masked version'): [B, T] per-frame loss.  On the GPU one launch per call (round 5); the stock
-        operator chain on the expanded distance matrix below serves reduction='none', odd codeword widths and, beyond the resident kernel's shapes, adaptive_margin."""
+        operator chain on the expanded distance matrix below serves reduction='none', widths that are no multiple of 16 and, beyond the resident kernel's shapes, adaptive_margin."""
         B, T, D = prd_quant.shape
         if (reduction in ('mean', 'sum') and hiploss.usable(prd_quant)
                 and (hiploss.triple_resident(self.dim, self.n_embed)
-                     or (not adaptive_margin and hiploss.triple_kernel_takes(self.dim, self.n_embed)))):
+                     or (not adaptive_margin and (hiploss.triple_kernel_takes(self.dim, self.n_embed)
+                                                  or hiploss.triple_wide_takes(1, self.dim, self.n_embed))))):
             # one launch: all K distances, the hinge and its gradient per frame (csrc/losses.hip triple_loss_kernel with the
-            # codebook in LDS; csrc/triple_stream.inc for d = 256 / 512 or a codebook beyond LDS)
+            # codebook in LDS; csrc/triple_stream.inc for d = 256 / 512 or a codebook beyond LDS); any other width that is a
+            # multiple of 16, up to 2048 (the k-means unit codebooks: d = 768 / 1024): the two GEMM-shaped launches of
+            # csrc/triple_wide.inc
             embed_t, enorm = hipvq.vq_prepare(self.embed.unsqueeze(0).contiguous(), frames=0)
             return hiploss.triple_loss(prd_quant.reshape(-1, D), trg_quant.reshape(-1, 1), embed_t, enorm, reduction,
                                        margin).reshape(B, T)

@@ -3,7 +3,10 @@
 codebook fits LDS, the resident triple_loss_kernel for scale) next to the stock operator chain the modules fall back to, on the
 same tensors, interleaved call by call in one process.  N = the frames per stage of BASELINE config #4 at B = 64 (6 400 at the
 coarse stage, 25 600 at the fine one).  Device events around every call, median of the timed calls after a warm-up, an otherwise
-idle process; profiles/triple_stream.md holds the table."""
+idle process; profiles/triple_stream.md holds the table.
+SET=wide: the single wide heads of the k-means unit codebooks (d = 768 / 1024, K = 500 / 2000; csrc/triple_wide.inc) at N = 51 200
+frames instead, with the peak of torch.cuda.max_memory_allocated over one forward + backward of either form above what is
+allocated before it, and the times of the kernel's two launches from the library's launch log; profiles/triple_wide.md."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'msmc-tts_amd')]
@@ -12,7 +15,8 @@ import torch
 from msmctts_amd.hip import lib, losses, vq
 
 dev = torch.device('cuda:0')
-NS = [int(v) for v in os.environ.get('NS', '6400,25600').split(',')]
+WIDE = os.environ.get('SET', 'stream') == 'wide'
+NS = [int(v) for v in os.environ.get('NS', '51200' if WIDE else '6400,25600').split(',')]
 ROUNDS = int(os.environ.get('ROUNDS', '30'))
 
 
@@ -44,9 +48,40 @@ def one(fn, p, w):
     return s, t
 
 
+def peak_mb(fn, p, w):
+    """peak of the allocator over one forward + backward, above what is allocated before it"""
+    p.grad = None
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    (fn(p) * w).sum().backward()
+    torch.cuda.synchronize()
+    p.grad = None
+    return (torch.cuda.max_memory_allocated() - base) / 1e6
+
+
+def launches(fn, p):
+    """(name, us) of the library's launches during one forward"""
+    import ctypes
+    L = lib.get()
+    torch.cuda.synchronize()
+    L.msmc_prof_enable(1)
+    with torch.no_grad():
+        fn(p)
+    torch.cuda.synchronize()
+    L.msmc_prof_enable(0)
+    out = []
+    name, ms = ctypes.create_string_buffer(128), ctypes.c_float()
+    for i in range(L.msmc_prof_count()):
+        if L.msmc_prof_read(i, name, 128, ctypes.byref(ms)) == 0:
+            out.append((name.value.decode(), ms.value * 1e3))
+    return out
+
+
 print('%-12s %7s | %-26s %9s %9s | %-12s %9s | ratio | max |dloss| max |dgrad|' %
       ('H x d x K', 'N', 'kernel', 'us', 'MB', 'reference', 'us'))
-for H, d, K in ((1, 256, 512), (2, 128, 512), (4, 64, 256)):
+for H, d, K in (((1, 768, 500), (1, 768, 2000), (1, 1024, 500), (1, 1024, 2000)) if WIDE else
+                ((1, 256, 512), (2, 128, 512), (4, 64, 256))):
     D = H * d
     g = torch.Generator().manual_seed(0)
     embed = torch.randn(H, d, K, generator=g).to(dev)
@@ -78,5 +113,15 @@ for H, d, K in ((1, 256, 512), (2, 128, 512), (4, 64, 256)):
         print('%-12s %7d | %-26s %9.1f %9.2f | %-12s %9.1f | %5.2f | %.3e %.3e' %
               ('%dx%dx%d' % (H, d, K), N, name, tk, byts / 1e6, 'stock chain', ts, ts / tk,
                float((lk - ls).abs().max()), float((gk - gs).abs().max())))
+        if WIDE:
+            mk, ms_ = peak_mb(fk, p, w), peak_mb(fs, p, w)
+            print('    peak MB above the inputs: kernel %.1f, stock chain %.1f (the mask: %.1f MB)' % (mk, ms_, N * ((K + 63) // 64) * 8 / 1e6))
+            for nm, us in launches(fk, p):
+                # fp32 MFMA roof 157.3 TFLOP/s; 2 N K d flops per launch.  HBM roof 8 TB/s over the compulsory bytes: pass 1 reads
+                # p and the codebook and writes the mask and lossh, pass 2 reads the mask and the codebook and writes gp
+                byts1 = 4.0 * N * d + 4.0 * K * (d + 1) + N * ((K + 63) // 64) * 8 + 12.0 * N
+                tf = 2.0 * N * K * d / (us * 1e-6) / 1e12
+                print('    %-28s %9.1f us  %6.1f TFLOP/s = %4.1f %% of the fp32 MFMA roof, %4.1f %% of the HBM roof' %
+                      (nm, us, tf, 100 * tf / 157.3, 100 * byts1 / (us * 1e-6) / 8e12))
         sys.stdout.flush()
         del p, trg, near, w, lk, ls, gk, gs
