@@ -227,8 +227,8 @@ __global__ __launch_bounds__(256) void masked_mean_bwd_kernel(const TA* __restri
     }
 }
 
-template <int MODE>
 #define LOSS_WS_BX 64
+template <int MODE>
 static int loss_launch(const msmc_tensor_table* t, float target, float* out, const float* gout, bool bwd,
                        msmc_stream stream, float* part = nullptr) {
     if (!t || t->count <= 0 || t->count > MSMC_MAX_TENSORS) return MSMC_E_SHAPE;
@@ -407,6 +407,7 @@ static thread_local const char* msmc_loss_last = "";
 extern "C" const char* msmc_loss_last_kernel(void) { return msmc_loss_last; }
 
 #include "triple_stream.inc"
+#include "wide_tile.inc"
 #include "triple_wide.inc"
 
 extern "C" {
@@ -443,7 +444,7 @@ int msmc_triple_loss_stream(const float* p, const int64_t* trg, const float* emb
     if (((size_t)p | (size_t)embed_t | (size_t)gp) & 15) return MSMC_E_SHAPE;
     return triple_stream_launch(p, trg, embed_t, enorm, lossh, gp, N, D, H, K, margin, mean, chunk, stream);
 }
-size_t msmc_triple_loss_wide_workspace(int N, int d, int K) { return (N > 0 && trw_takes(d, K)) ? trw_workspace_bytes(N, K) : 0; }
+size_t msmc_triple_loss_wide_workspace(int N, int d, int K) { return (N > 0 && wide_takes(d, K)) ? trw_workspace_bytes(N, K) : 0; }
 int msmc_triple_loss_wide(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp,
                           int N, int d, int K, float margin, int mean, void* workspace, size_t workspace_bytes,
                           msmc_stream stream) {

@@ -5,11 +5,9 @@
 // and its running sum of active codewords in registers: at d = 1024 neither fits.  Here both halves of the work are GEMMs on
 // v_mfma_f32_16x16x4_f32 (exact fp32), in two launches with a bit mask of the active codewords between them:
 //
-// 1. triple_loss_wide_kernel: the K products p.e_k of a frame tile, as vq_search_wide_kernel (vq_wide.inc) forms them: frame
-//    tiles x centroid tiles of 64, the d axis in slices of 32 channels, one LDS buffer holding a slice of the frame rows
-//    followed by the same slice of the 64 centroid rows at a pitch of 36 floats, two such buffers (the rows of slice q + 1
-//    travel L2 -> registers -> the other buffer around the MFMA steps of slice q; one workgroup barrier per slice).  A wave owns
-//    16 frames x the whole centroid tile (four accumulators); NW = 1 / 2 / 4 waves make a workgroup (the launcher picks NW from
+// 1. triple_loss_wide_kernel: the K products p.e_k of a frame tile on the slice pipeline of wide_tile.inc (tiling, LDS buffers,
+//    hand-over, MFMA step and channel order: there), the pipeline of vq_search_wide_kernel (vq_wide.inc).  A wave owns
+//    16 frames x the whole centroid tile of 64; NW = 1 / 2 / 4 waves make a workgroup (the launcher picks NW from
 //    N: few frames still fill the CUs).  |p|^2 and pos = sum_c (p_c - e_trg,c)^2 come from global memory before the loop, lane
 //    group g of a frame taking the 16-byte pieces g, g + 4, ...  After a tile's last slice lane (f, g) holds the products of
 //    frame f with codewords 64 kt + 16 m + 4 g + r: t_k = pos - ((|p|^2 - 2 p.e_k) + |e_k|^2), active when t_k != 0 and
@@ -28,23 +26,13 @@
 // Order of arithmetic: fixed by (d, K) alone -- never by N, NW / WF, the grid or the other frames of a tile.  No atomics; every
 // global store is a vector-memory store.
 
-#define TRW_DS 32                    // channels per slice (pass 1)
-#define TRW_PITCH (TRW_DS + 4)       // floats per row of a slice buffer
-#define TRW_KT 64                    // codewords per centroid tile = bits per mask word
+// (a centroid tile of both passes is WIDE_KT = 64 codewords: the bits of a mask word)
 #define TRW_DC 128                   // channels per window (pass 2)
 #define TRW_EPITCH (TRW_DC + 4)      // floats per row of a window buffer
-#define TRW_MAX_D 2048
 
 // tests / tools (include/msmc_hip_debug.h): frames per workgroup of both launches, 16 / 32 / 64; 0 = the launcher's choice
 static int triple_wide_frames = 0;
 extern "C" void msmc_triple_wide_set_frames(int ft) { triple_wide_frames = ft; }
-
-// one 16-byte piece of a row-major [rows][d] matrix; zeros past the last row or the window's end
-MSMC_DEV f32x4 trw_piece(const float* __restrict__ m, int row, int rows, int d, int c, int cend) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < rows && c < cend) v = *(const f32x4*)(m + (size_t)row * d + c);
-    return v;
-}
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void triple_loss_wide_kernel(const float* __restrict__ p, const long long* __restrict__ trg,
@@ -53,49 +41,23 @@ __global__ __launch_bounds__(64 * NW) void triple_loss_wide_kernel(const float* 
                                                                    unsigned short* __restrict__ mask, int N, int d, int K,
                                                                    float margin, float lscale) {
     MSMC_DYN_LDS(smem);
-    constexpr int NTHR = 64 * NW, FT = 16 * NW, ROWS = FT + TRW_KT;
-    constexpr int NST = (ROWS * (TRW_DS / 4) + NTHR - 1) / NTHR;      // 16-byte pieces per work-item per slice
-    float* sl = (float*)smem;                                         // [2][ROWS][TRW_PITCH]: frame rows, then centroid rows
-    float* en = sl + 2 * ROWS * TRW_PITCH;                            // [2][TRW_KT]
+    constexpr int NTHR = 64 * NW, FT = 16 * NW, KT = WIDE_KT, ROWS = FT + KT;
+    float* sl = (float*)smem;                                         // [2][ROWS][WIDE_PITCH]: frame rows, then centroid rows
+    float* en = sl + 2 * ROWS * WIDE_PITCH;                           // [2][KT]
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int f = lane & 15, g = lane >> 4;
     const int n0 = blockIdx.x * FT;
-    const int nds = (d + TRW_DS - 1) / TRW_DS;
-    const int nkt = (K + TRW_KT - 1) / TRW_KT;
+    const int nds = (d + WIDE_DS - 1) / WIDE_DS;
+    const int nkt = (K + KT - 1) / KT;
     const int total = nkt * nds;
     const int n = n0 + 16 * w + f;
     const bool ok = n < N;                                            // (lanes past the last frame compute on frame N-1 and
     const int nl = ok ? n : N - 1;                                    //  store nothing)
 
-    f32x4 st[NST];
-    auto stage_load = [&](int q) {
-        const int kt = q / nds, s0 = (q - kt * nds) * TRW_DS;
-        const int sh = d - s0 < TRW_DS ? 2 : 3;                       // 16-byte pieces per row: 4 (d % 32 == 16, last slice) or 8
-#pragma unroll
-        for (int i = 0; i < NST; ++i) {
-            const int e = i * NTHR + tid;
-            const int r = e >> sh, c = s0 + 4 * (e & ((1 << sh) - 1));
-            st[i] = r < FT ? trw_piece(p, n0 + r, N, d, c, d) : trw_piece(embed_t, kt * TRW_KT + r - FT, r < ROWS ? K : 0, d, c, d);
-        }
-    };
-    auto stage_store = [&](int q, float* dst) {
-        const int kt = q / nds, s0 = (q - kt * nds) * TRW_DS;
-        const int sh = d - s0 < TRW_DS ? 2 : 3;
-#pragma unroll
-        for (int i = 0; i < NST; ++i) {
-            const int e = i * NTHR + tid;
-            const int r = e >> sh, c4 = e & ((1 << sh) - 1);
-            if (r < ROWS) *(f32x4*)(dst + r * TRW_PITCH + 4 * c4) = st[i];
-        }
-    };
-    auto norm_of = [&](int kt) {                                      // (NTHR >= TRW_KT: one norm per work-item)
-        const int k = kt * TRW_KT + tid;
-        return (tid < TRW_KT && k < K) ? enorm[k] : 0.f;
-    };
-
-    stage_load(0);
-    stage_store(0, sl);
-    if (tid < TRW_KT) en[tid] = norm_of(0);
+    WideStage<FT, KT, NTHR> stage;                                    // (NTHR >= KT: one norm per work-item; 0.f past K)
+    stage.load(p, n0, N, embed_t, 0, K, d, 0, tid);
+    stage.store(sl, d, 0, tid);
+    wide_norm_store(en, 0, KT, tid, wide_norm_fetch(enorm, 0, KT, K, tid, 0.f));
 
     // |p|^2 and the direct squared difference to the target's row (global memory / L2): lane group g takes pieces g, g + 4, ...
     long long t = trg[nl];
@@ -128,35 +90,25 @@ __global__ __launch_bounds__(64 * NW) void triple_loss_wide_kernel(const float* 
     f32x4 acc[4];
     for (int q = 0; q < total; ++q) {
         const int kt = q / nds, s = q - kt * nds;
-        const int nt = d - s * TRW_DS < TRW_DS ? 1 : 2;               // 16-channel groups of this slice
         const bool more = q + 1 < total;
         const bool next_tile = more && s + 1 == nds;
+        const int kt1 = next_tile ? kt + 1 : kt, s1 = next_tile ? 0 : s + 1;      // slice q + 1
         float nn = 0.f;
-        if (more) stage_load(q + 1);
-        if (next_tile) nn = norm_of(kt + 1);
+        if (more) stage.load(p, n0, N, embed_t, kt1 * KT, K, d, s1 * WIDE_DS, tid);
+        if (next_tile) nn = wide_norm_fetch(enorm, kt1, KT, K, tid, 0.f);
         if (s == 0) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        const float* slc = sl + buf * ROWS * TRW_PITCH;
-        const float* fb = slc + (16 * w + f) * TRW_PITCH + 4 * g;
-        const float* cb = slc + (FT + f) * TRW_PITCH + 4 * g;
-        for (int tt = 0; tt < nt; ++tt) {
-            const f32x4 bv = *(const f32x4*)(fb + 16 * tt);
-            f32x4 av[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) av[m] = *(const f32x4*)(cb + m * 16 * TRW_PITCH + 16 * tt);
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[m] = mfma_f32_16x16x4(av[m][jj], bv[jj], acc[m]);
-        }
-        if (more) stage_store(q + 1, sl + (buf ^ 1) * ROWS * TRW_PITCH);
-        if (next_tile && tid < TRW_KT) en[((kt + 1) & 1) * TRW_KT + tid] = nn;
+        const float* slc = sl + buf * ROWS * WIDE_PITCH;
+        wide_slice_mfma(slc + (16 * w + f) * WIDE_PITCH + 4 * g, slc + (FT + f) * WIDE_PITCH + 4 * g, wide_groups(d, s * WIDE_DS),
+                        acc, [](const f32x4&) {});
+        if (more) stage.store(sl + (buf ^ 1) * ROWS * WIDE_PITCH, d, s1 * WIDE_DS, tid);
+        if (next_tile) wide_norm_store(en, kt1, KT, tid, nn);
 
         if (s == nds - 1) {   // the tile's last slice: the hinge decisions of this lane's 16 codewords
-            const float* enc = en + (kt & 1) * TRW_KT + 4 * g;
-            const int k0 = kt * TRW_KT + 4 * g;
+            const float* enc = wide_norm_tile(en, kt, KT) + 4 * g;
+            const int k0 = kt * KT + 4 * g;
             unsigned int bits = 0u;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
@@ -189,8 +141,8 @@ __global__ __launch_bounds__(256) void triple_grad_wide_kernel(const long long* 
                                                               int N, int d, int K, float gscale) {
     MSMC_DYN_LDS(smem);
     constexpr int WCH = 4 / WF, FT = 16 * WF, CW = TRW_DC / WCH, NB = CW / 64;
-    constexpr int NST = TRW_KT * (TRW_DC / 4) / 256;                  // 16-byte pieces per work-item per tile
-    float* eb = (float*)smem;                                         // [2][TRW_KT][TRW_EPITCH]
+    constexpr int NST = WIDE_KT * (TRW_DC / 4) / 256;                 // 16-byte pieces per work-item per tile
+    float* eb = (float*)smem;                                         // [2][WIDE_KT][TRW_EPITCH]
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int f = lane & 15, g = lane >> 4;
     const int wf = w / WCH, wc = w - wf * WCH;
@@ -198,14 +150,14 @@ __global__ __launch_bounds__(256) void triple_grad_wide_kernel(const long long* 
     const bool ok = n < N;
     const int c0 = blockIdx.y * TRW_DC;
     const int cw = d - c0 < TRW_DC ? d - c0 : TRW_DC;                 // channels of this window (a multiple of 16)
-    const int nkt = (K + TRW_KT - 1) / TRW_KT;
+    const int nkt = (K + WIDE_KT - 1) / WIDE_KT;
 
     f32x4 st[NST];
     auto stage_load = [&](int kt) {                                   // (zeros past K and past the window: they are multiplied)
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
             const int e = i * 256 + tid;
-            st[i] = trw_piece(embed_t, kt * TRW_KT + (e >> 5), K, d, c0 + 4 * (e & 31), c0 + cw);
+            st[i] = wide_piece(embed_t, kt * WIDE_KT + (e >> 5), K, d, c0 + 4 * (e & 31), c0 + cw);
         }
     };
     auto stage_store = [&](float* dst) {
@@ -237,7 +189,7 @@ __global__ __launch_bounds__(256) void triple_grad_wide_kernel(const long long* 
         }
 #pragma unroll
         for (int a = 0; a < 4 * NB; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float* ebc = eb + buf * TRW_KT * TRW_EPITCH + 4 * g * TRW_EPITCH + wc * CW + 4 * f;
+        const float* ebc = eb + buf * WIDE_KT * TRW_EPITCH + 4 * g * TRW_EPITCH + wc * CW + 4 * f;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const float b = (float)((h >> j) & 1u);
@@ -258,7 +210,7 @@ __global__ __launch_bounds__(256) void triple_grad_wide_kernel(const long long* 
             sc[a] = (tt - s[a]) - y;
             s[a] = tt;
         }
-        if (more) stage_store(eb + (buf ^ 1) * TRW_KT * TRW_EPITCH);
+        if (more) stage_store(eb + (buf ^ 1) * WIDE_KT * TRW_EPITCH);
         h = hn;
         __syncthreads();         // tile kt + 1 is complete, and nobody reads tile kt any more
         buf ^= 1;
@@ -291,14 +243,13 @@ typedef void (*triple_loss_wide_fn)(const float*, const long long*, const float*
                                     int, float, float);
 typedef void (*triple_grad_wide_fn)(const long long*, const float*, const unsigned short*, float*, int, int, int, float);
 
-static inline bool trw_takes(int d, int K) { return d >= 16 && d <= TRW_MAX_D && d % 16 == 0 && K >= 1; }
 // the mask: a 64-bit word per (frame, centroid tile)
-static inline size_t trw_workspace_bytes(int N, int K) { return (size_t)N * ((K + TRW_KT - 1) / TRW_KT) * 8; }
+static inline size_t trw_workspace_bytes(int N, int K) { return (size_t)N * ((K + WIDE_KT - 1) / WIDE_KT) * 8; }
 
 static int triple_wide_launch(const float* p, const int64_t* trg, const float* embed_t, const float* enorm, float* lossh, float* gp,
                               int N, int d, int K, float margin, int mean, void* workspace, size_t workspace_bytes,
                               msmc_stream stream) {
-    if (N < 0 || !trw_takes(d, K)) return MSMC_E_SHAPE;
+    if (N < 0 || !wide_takes(d, K)) return MSMC_E_SHAPE;
     if (N == 0) return 0;
     if (!workspace || workspace_bytes < trw_workspace_bytes(N, K)) return MSMC_E_WORKSPACE;
     // frames per workgroup: 64 once such workgroups fill every CU, fewer while they would not
@@ -308,8 +259,8 @@ static int triple_wide_launch(const float* p, const int64_t* trg, const float* e
     const int ft2 = ft == 64 ? 64 : 32;                              // (the second launch has d / 128 workgroups per frame tile)
     triple_loss_wide_fn f1 = nw == 4 ? triple_loss_wide_kernel<4> : nw == 2 ? triple_loss_wide_kernel<2> : triple_loss_wide_kernel<1>;
     triple_grad_wide_fn f2 = ft2 == 64 ? triple_grad_wide_kernel<4> : triple_grad_wide_kernel<2>;
-    const size_t lds1 = ((size_t)2 * (ft + TRW_KT) * TRW_PITCH + 2 * TRW_KT) * sizeof(float);
-    const size_t lds2 = (size_t)2 * TRW_KT * TRW_EPITCH * sizeof(float);
+    const size_t lds1 = wide_lds_floats(ft, WIDE_KT) * sizeof(float);
+    const size_t lds2 = (size_t)2 * WIDE_KT * TRW_EPITCH * sizeof(float);
     int rc = msmc_allow_lds((const void*)f1, (int)lds1);
     if (rc) return rc;
     rc = msmc_allow_lds((const void*)f2, (int)lds2);

@@ -361,6 +361,7 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
 
 #include "vq_shortlist.inc"
 #include "vq_stream.inc"
+#include "wide_tile.inc"
 #include "vq_wide.inc"
 
 typedef void (*vq_search_reg_fn)(const float*, const float*, const float*, float*, float*, int64_t*, int, int, int, int,

@@ -5,7 +5,7 @@ import ctypes
 
 import torch
 
-from . import lib
+from . import lib, vq
 
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 
@@ -190,9 +190,8 @@ def triple_kernel_takes(d, K):
     return d in STREAM_DIMS and K >= 1
 
 
-def triple_wide_takes(H, d, K):
-    """the shapes ``msmc_triple_loss_wide`` (csrc/triple_wide.inc) takes: one head, d % 16 == 0, 16 <= d <= 2048, any K >= 1"""
-    return H == 1 and d % 16 == 0 and 16 <= d <= 2048 and K >= 1
+# the shapes ``msmc_triple_loss_wide`` (csrc/triple_wide.inc) takes: those of the wide search, csrc/wide_tile.inc wide_takes
+triple_wide_takes = vq.wide_takes
 
 
 class _TripleLoss(torch.autograd.Function):

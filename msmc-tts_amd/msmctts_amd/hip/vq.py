@@ -57,7 +57,8 @@ E_SHAPE = -2                # MSMC_E_SHAPE of include/msmc_hip.h
 
 
 def wide_takes(H, d, K):
-    """the shapes ``msmc_vq_search_wide`` takes: one head, d % 16 == 0, 16 <= d <= 2048, any K >= 1"""
+    """the shapes the wide kernels (``msmc_vq_search_wide``, ``msmc_triple_loss_wide``; csrc/wide_tile.inc wide_takes) take: one
+    head, d % 16 == 0, 16 <= d <= 2048, any K >= 1"""
     return H == 1 and d % 16 == 0 and 16 <= d <= 2048 and K >= 1
 
 
