@@ -1,40 +1,11 @@
-// bn_common.inc -- row-vector access, Chan merge and lane geometry shared by the channels-last statistics kernels
+// bn_common.inc -- row-vector width, Chan merge and lane geometry shared by the channels-last statistics kernels
 // (csrc/norm.hip msmc_bn_*, csrc/tdnn.hip msmc_relu_bn_* / msmc_se_* / msmc_asp_*).  Included after <msmc_rt.hpp>.
 #pragma once
+#include "elem.inc"
+// a row moves as 16-byte vectors (el_ldv / el_stv of elem.inc): 4 fp32 or 8 bf16 channels per lane
 template <typename T> struct bn_vec { static constexpr int V = 4; };
 template <> struct bn_vec<unsigned short> { static constexpr int V = 8; };
 
-template <int V> MSMC_DEV void bn_ld(const float* p, long i, float (&o)[V]) {
-#pragma unroll
-    for (int h = 0; h < V / 4; ++h) {
-        const f32x4 t = *(const f32x4*)(p + i + 4 * h);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[4 * h + q] = t[q];
-    }
-}
-MSMC_DEV void bn_ld(const unsigned short* p, long i, float (&o)[8]) {
-    const u32x4 t = *(const u32x4*)(p + i);
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        o[2 * h] = __uint_as_float(t[h] << 16);
-        o[2 * h + 1] = __uint_as_float(t[h] & 0xffff0000u);
-    }
-}
-template <int V> MSMC_DEV void bn_st(float* p, long i, const float (&v)[V]) {
-#pragma unroll
-    for (int h = 0; h < V / 4; ++h) {
-        f32x4 t;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) t[q] = v[4 * h + q];
-        *(f32x4*)(p + i + 4 * h) = t;
-    }
-}
-MSMC_DEV void bn_st(unsigned short* p, long i, const float (&v)[8]) {
-    u32x4 t;
-#pragma unroll
-    for (int h = 0; h < 4; ++h) t[h] = (unsigned)f32_to_bf16_bits(v[2 * h]) | ((unsigned)f32_to_bf16_bits(v[2 * h + 1]) << 16);
-    *(u32x4*)(p + i) = t;
-}
 // (n, mean, m2) <- (n, mean, m2) merged with (nb, mb, m2b): Chan, Golub & LeVeque
 MSMC_DEV void bn_chan(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
     if (nb == 0.f) return;

@@ -3,6 +3,7 @@
 // group size, csrc/wnorm.hip.  Included after <msmc_rt.hpp> and <msmc_hip.h>.
 #pragma once
 #include <cstdio>
+#include "elem.inc"
 
 #define CV_BM 128
 
@@ -41,18 +42,11 @@ static bool cv_desc_ok(const msmc_conv_desc* d) { return d->B > 0 && d->Cin > 0 
 // the launcher's own answer)
 static int cv_launched(int rc) { return rc ? (rc < 0 ? rc : -rc) : 1; }
 
-template <typename T> struct Elt;
-template <> struct Elt<float> {
-    static constexpr int VEC = 4;       // elements per 16 bytes
-    static constexpr int CK = 16;       // channels per 64-byte chunk
-    static MSMC_DEV_INLINE float ld(const float* p) { return *p; }
-    static MSMC_DEV_INLINE void st(float* p, float v) { *p = v; }
-};
-template <> struct Elt<unsigned short> {
-    static constexpr int VEC = 8;
-    static constexpr int CK = 32;
-    static MSMC_DEV_INLINE float ld(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-    static MSMC_DEV_INLINE void st(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
+template <typename T> struct Elt {      // float, or unsigned short (bf16 bits): el_ld / el_st of elem.inc take nothing else
+    static constexpr int VEC = 16 / (int)sizeof(T);     // elements per 16 bytes
+    static constexpr int CK = 64 / (int)sizeof(T);      // channels per 64-byte chunk
+    static MSMC_DEV_INLINE float ld(const T* p) { return el_ld(p); }
+    static MSMC_DEV_INLINE void st(T* p, float v) { el_st(p, v); }
 };
 
 MSMC_DEV int reflect_index(int i, int n) {

@@ -7,27 +7,7 @@
 // the launches are hipGraph-capturable.
 #include <msmc_rt.hpp>
 #include <msmc_hip.h>
-
-template <typename T> struct LEl;
-template <> struct LEl<float> {
-    static MSMC_DEV_INLINE float ld(const float* p) { return *p; }
-    static MSMC_DEV_INLINE void st(float* p, float v) { *p = v; }
-};
-template <> struct LEl<unsigned short> {
-    static MSMC_DEV_INLINE float ld(const unsigned short* p) { return bf16_bits_to_f32(*p); }
-    static MSMC_DEV_INLINE void st(unsigned short* p, float v) { *p = f32_to_bf16_bits(v); }
-};
-
-MSMC_DEV float loss_block_sum(float v, float* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
+#include "elem.inc"
 
 // MODE 0: L1(a, b)   MODE 1: (a - target)^2
 // part != NULL: the block's sum goes to part[tensor * gridDim.x + block] (loss_multi_final_kernel adds them in a fixed order:
@@ -46,37 +26,29 @@ __global__ __launch_bounds__(256) void loss_multi_fwd_kernel(msmc_tensor_table t
     const bool vec = ((((size_t)a) | ((size_t)b)) & 15) == 0;
     const long nv = vec ? n / VE : 0;
     for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long)gridDim.x * 256) {
-        const u32x4 av4 = *(const u32x4*)(a + v * VE);
-        u32x4 bv4 = {0u, 0u, 0u, 0u};
-        if (MODE == 0) bv4 = *(const u32x4*)(b + v * VE);
+        float av[VE], bv[VE];
+        el_ldv(a + v * VE, av);
+        if (MODE == 0) el_ldv(b + v * VE, bv);
 #pragma unroll
         for (int q = 0; q < VE; ++q) {
-            float av, bv;
-            if (sizeof(T) == 4) {
-                av = __uint_as_float(av4[q & 3]);
-                bv = __uint_as_float(bv4[q & 3]);
-            } else {
-                av = bf16_bits_to_f32((unsigned short)(av4[(q >> 1) & 3] >> (16 * (q & 1))));
-                bv = bf16_bits_to_f32((unsigned short)(bv4[(q >> 1) & 3] >> (16 * (q & 1))));
-            }
             if (MODE == 0) {
-                s = s + fabsf(av - bv);
+                s = s + fabsf(av[q] - bv[q]);
             } else {
-                const float dlt = av - target;
+                const float dlt = av[q] - target;
                 s = fmaf(dlt, dlt, s);
             }
         }
     }
     for (long e = nv * VE + (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-        const float av = LEl<T>::ld(a + e);
+        const float av = el_ld(a + e);
         if (MODE == 0) {
-            s = s + fabsf(av - LEl<T>::ld(b + e));
+            s = s + fabsf(av - el_ld(b + e));
         } else {
             const float dlt = av - target;
             s = fmaf(dlt, dlt, s);
         }
     }
-    s = loss_block_sum(s, red);
+    s = block_tree_sum<false>(s, red);
     if (part) {
         if (threadIdx.x == 0) part[(size_t)i * gridDim.x + blockIdx.x] = s;
         return;
@@ -94,7 +66,7 @@ __global__ __launch_bounds__(256) void loss_multi_final_kernel(msmc_tensor_table
         for (int x = 0; x < bx; ++x) ti = ti + part[(size_t)i * bx + x];
         s = s + ti / (float)t.n[i];
     }
-    s = loss_block_sum(s, red);
+    s = block_tree_sum<false>(s, red);
     if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -111,48 +83,30 @@ __global__ __launch_bounds__(256) void loss_multi_bwd_kernel(msmc_tensor_table t
     const bool vec = ((((size_t)a) | ((size_t)b) | ((size_t)ga)) & 15) == 0;
     const long nv = vec ? n / VE : 0;
     for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long)gridDim.x * 256) {
-        const u32x4 av4 = *(const u32x4*)(a + v * VE);
-        u32x4 bv4 = {0u, 0u, 0u, 0u};
-        if (MODE == 0) bv4 = *(const u32x4*)(b + v * VE);
-        float gq[VE];
+        float av[VE], bv[VE], gq[VE];
+        el_ldv(a + v * VE, av);
+        if (MODE == 0) el_ldv(b + v * VE, bv);
 #pragma unroll
         for (int q = 0; q < VE; ++q) {
-            float av, bv;
-            if (sizeof(T) == 4) {
-                av = __uint_as_float(av4[q & 3]);
-                bv = __uint_as_float(bv4[q & 3]);
-            } else {
-                av = bf16_bits_to_f32((unsigned short)(av4[(q >> 1) & 3] >> (16 * (q & 1))));
-                bv = bf16_bits_to_f32((unsigned short)(bv4[(q >> 1) & 3] >> (16 * (q & 1))));
-            }
             if (MODE == 0) {
-                const float dlt = av - bv;
+                const float dlt = av[q] - bv[q];
                 gq[q] = dlt > 0.f ? scale : (dlt < 0.f ? -scale : 0.f);
             } else {
-                gq[q] = 2.f * (av - target) * scale;
+                gq[q] = 2.f * (av[q] - target) * scale;
             }
         }
-        u32x4 o;
-        if (sizeof(T) == 4) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = __float_as_uint(gq[q]);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                o[q] = (unsigned int)f32_to_bf16_bits(gq[(2 * q) % VE]) | ((unsigned int)f32_to_bf16_bits(gq[(2 * q + 1) % VE]) << 16);
-        }
-        *(u32x4*)(ga + v * VE) = o;
+        el_stv(ga, v * VE, gq);
     }
     for (long e = nv * VE + (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-        const float av = LEl<T>::ld(a + e);
+        const float av = el_ld(a + e);
         float g;
         if (MODE == 0) {
-            const float dlt = av - LEl<T>::ld(b + e);
+            const float dlt = av - el_ld(b + e);
             g = dlt > 0.f ? scale : (dlt < 0.f ? -scale : 0.f);
         } else {
             g = 2.f * (av - target) * scale;
         }
-        LEl<T>::st(ga + e, g);
+        el_st(ga + e, g);
     }
 }
 
@@ -181,15 +135,15 @@ __global__ __launch_bounds__(256) void masked_mean_partial_kernel(const TA* __re
     const long n = L * C, base = (long)bi * T * C;
     float s = 0.f;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)MM_BX * 256) {
-        const float av = LEl<TA>::ld(a + base + e);
+        const float av = el_ld(a + base + e);
         if (MODE == 0) {
             s = s + av;
         } else {
-            const float dlt = av - LEl<TB>::ld(b + base + e);
+            const float dlt = av - el_ld(b + base + e);
             s = fmaf(dlt, dlt, s);
         }
     }
-    s = loss_block_sum(s, red);
+    s = block_tree_sum<false>(s, red);
     if (threadIdx.x == 0) part[bi * MM_BX + blockIdx.x] = s;
 }
 // out[0] = (sum of the partials in index order) / sum_b len_b / C;  out[1] = 1 / (sum_b len_b * C) for the backward pass
@@ -199,7 +153,7 @@ __global__ __launch_bounds__(256) void masked_mean_final_kernel(const float* __r
     __shared__ float red[256];
     float s = 0.f;
     for (int k = threadIdx.x; k < nparts; k += 256) s = s + part[k];
-    s = loss_block_sum(s, red);
+    s = block_tree_sum<false>(s, red);
     if (threadIdx.x == 0) {
         float tot = 0.f;                                   // (the reference sums the lengths as they are: no clamp to T)
         for (int b = 0; b < B; ++b) tot = tot + (float)loss_len(len, is64, b);
@@ -221,9 +175,9 @@ __global__ __launch_bounds__(256) void masked_mean_bwd_kernel(const TA* __restri
     const float k = gout[0] * out[1];
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
         float g = 0.f;
-        if (e < nv) g = MODE == 0 ? k : 2.f * (LEl<TA>::ld(a + base + e) - LEl<TB>::ld(b + base + e)) * k;
-        if (ga) LEl<TA>::st(ga + base + e, g);
-        if (gb) LEl<TB>::st(gb + base + e, -g);
+        if (e < nv) g = MODE == 0 ? k : 2.f * (el_ld(a + base + e) - el_ld(b + base + e)) * k;
+        if (ga) el_st(ga + base + e, g);
+        if (gb) el_st(gb + base + e, -g);
     }
 }
 
@@ -240,24 +194,24 @@ static int loss_launch(const msmc_tensor_table* t, float target, float* out, con
     long bx = (nmax + 4095) / 4096;
     if (bx > 256) bx = 256;
     dim3 grid((unsigned)bx, (unsigned)t->count);
+    const dim3 g2(LOSS_WS_BX, (unsigned)t->count);
+#define LOSS_FWD_WS(T_) MSMC_LAUNCH((loss_multi_fwd_kernel<T_, MODE>), g2, dim3(256), 0, (msmc_stream_t)stream, *t, target, out, part)
+#define LOSS_FWD(T_) MSMC_LAUNCH((loss_multi_fwd_kernel<T_, MODE>), grid, dim3(256), 0, (msmc_stream_t)stream, *t, target, out, (float*)nullptr)
+#define LOSS_BWD(T_) MSMC_LAUNCH((loss_multi_bwd_kernel<T_, MODE>), grid, dim3(256), 0, (msmc_stream_t)stream, *t, target, gout)
     if (!bwd && part) {
-        const dim3 g2(LOSS_WS_BX, (unsigned)t->count);
-        if (t->dtype == 0) MSMC_LAUNCH((loss_multi_fwd_kernel<float, MODE>), g2, dim3(256), 0, (msmc_stream_t)stream, *t, target, out, part);
-        else if (t->dtype == 1) MSMC_LAUNCH((loss_multi_fwd_kernel<unsigned short, MODE>), g2, dim3(256), 0, (msmc_stream_t)stream, *t, target, out, part);
-        else return MSMC_E_SHAPE;
+        MSMC_BY_DTYPE(t->dtype, LOSS_FWD_WS);
         int rc = msmc_check_launch();
         if (rc) return rc;
         MSMC_LAUNCH(loss_multi_final_kernel, dim3(1), dim3(256), 0, (msmc_stream_t)stream, *t, (const float*)part, LOSS_WS_BX, out);
     } else if (!bwd) {
         MSMC_LAUNCH(loss_zero_kernel, dim3(1), dim3(64), 0, (msmc_stream_t)stream, out);
-        if (t->dtype == 0) MSMC_LAUNCH((loss_multi_fwd_kernel<float, MODE>), grid, dim3(256), 0, (msmc_stream_t)stream, *t, target, out, (float*)nullptr);
-        else if (t->dtype == 1) MSMC_LAUNCH((loss_multi_fwd_kernel<unsigned short, MODE>), grid, dim3(256), 0, (msmc_stream_t)stream, *t, target, out, (float*)nullptr);
-        else return MSMC_E_SHAPE;
+        MSMC_BY_DTYPE(t->dtype, LOSS_FWD);
     } else {
-        if (t->dtype == 0) MSMC_LAUNCH((loss_multi_bwd_kernel<float, MODE>), grid, dim3(256), 0, (msmc_stream_t)stream, *t, target, gout);
-        else if (t->dtype == 1) MSMC_LAUNCH((loss_multi_bwd_kernel<unsigned short, MODE>), grid, dim3(256), 0, (msmc_stream_t)stream, *t, target, gout);
-        else return MSMC_E_SHAPE;
+        MSMC_BY_DTYPE(t->dtype, LOSS_BWD);
     }
+#undef LOSS_FWD_WS
+#undef LOSS_FWD
+#undef LOSS_BWD
     return msmc_check_launch();
 }
 

@@ -10,11 +10,7 @@
 // salt, element index), so a hipGraph replay draws fresh masks when the seed word is advanced inside the graph.
 #include <msmc_rt.hpp>
 #include <msmc_hip.h>
-
-MSMC_DEV float nm_ld(const float* p, long i) { return p[i]; }
-MSMC_DEV float nm_ld(const unsigned short* p, long i) { return bf16_bits_to_f32(p[i]); }
-MSMC_DEV void nm_st(float* p, long i, float v) { p[i] = v; }
-MSMC_DEV void nm_st(unsigned short* p, long i, float v) { p[i] = f32_to_bf16_bits(v); }
+#include "elem.inc"
 
 // keep-probability test: 32-bit mix of (key, element index) against the drop threshold
 MSMC_DEV bool nm_keep(unsigned long long key, unsigned long long idx, unsigned int thresh) {
@@ -28,55 +24,7 @@ MSMC_DEV unsigned long long nm_key(const long long* seed, long long salt) {
     const unsigned long long s = seed ? (unsigned long long)seed[0] : 0ull;
     return s * 0xD1342543DE82EF95ull + (unsigned long long)salt * 0x2545F4914F6CDD1Dull + 0x632BE59BD9B4E019ull;
 }
-MSMC_DEV float nm_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = v + wave_xor(v, m);
-    return v;
-}
-
 #define NM_MAXE 16          // elements per lane: C <= 1024
-
-// V consecutive elements of a row as one vector access (V = 4: 16 bytes of fp32, 8 bytes of bf16; V = 1: scalar)
-template <int V> MSMC_DEV void nm_ldv(const float* p, long i, float (&o)[V]) {
-    if constexpr (V == 4) {
-        const f32x4 t = *(const f32x4*)(p + i);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = t[q];
-    } else {
-        o[0] = p[i];
-    }
-}
-template <int V> MSMC_DEV void nm_ldv(const unsigned short* p, long i, float (&o)[V]) {
-    if constexpr (V == 4) {
-        const u32x2 t = *(const u32x2*)(p + i);
-        o[0] = __uint_as_float(t[0] << 16);
-        o[1] = __uint_as_float(t[0] & 0xffff0000u);
-        o[2] = __uint_as_float(t[1] << 16);
-        o[3] = __uint_as_float(t[1] & 0xffff0000u);
-    } else {
-        o[0] = bf16_bits_to_f32(p[i]);
-    }
-}
-template <int V> MSMC_DEV void nm_stv(float* p, long i, const float (&v)[V]) {
-    if constexpr (V == 4) {
-        f32x4 t;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) t[q] = v[q];
-        *(f32x4*)(p + i) = t;
-    } else {
-        p[i] = v[0];
-    }
-}
-template <int V> MSMC_DEV void nm_stv(unsigned short* p, long i, const float (&v)[V]) {
-    if constexpr (V == 4) {
-        u32x2 t;
-        t[0] = (unsigned)f32_to_bf16_bits(v[0]) | ((unsigned)f32_to_bf16_bits(v[1]) << 16);
-        t[1] = (unsigned)f32_to_bf16_bits(v[2]) | ((unsigned)f32_to_bf16_bits(v[3]) << 16);
-        *(u32x2*)(p + i) = t;
-    } else {
-        p[i] = f32_to_bf16_bits(v[0]);
-    }
-}
 
 // one wave per row: v = drop(x) + res; y = (v - mean) * rstd * gamma + beta, zeroed where keep_row == 0.
 // A lane owns the V-element groups (lane + 64 jj) * V .. + V of its row (V = 4 when C % 4 == 0: vector accesses).
@@ -104,8 +52,8 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const T* __restrict__ x
         if (c < C) {
             const long i = row * C + c;
             float a[V], r[V];
-            nm_ldv<V>(x, i, a);
-            if (res) nm_ldv<V>(res, i, r);
+            el_ldv<V>(x, i, a);
+            if (res) el_ldv<V>(res, i, r);
 #pragma unroll
             for (int q = 0; q < V; ++q) {
                 if (thresh) a[q] = nm_keep(key, (unsigned long long)(i + q), thresh) ? a[q] * scale : 0.f;
@@ -115,14 +63,14 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const T* __restrict__ x
             }
         }
     }
-    const float mean = nm_wave_sum(sum) / C;
+    const float mean = wave_xor_sum(sum) / C;
     float sq = 0.f;
 #pragma unroll
     for (int jj = 0; jj < NG; ++jj)
         if ((lane + 64 * jj) * V < C)
 #pragma unroll
             for (int q = 0; q < V; ++q) sq = fmaf(v[jj][q] - mean, v[jj][q] - mean, sq);
-    const float rstd = 1.f / sqrtf(nm_wave_sum(sq) / C + eps);
+    const float rstd = 1.f / sqrtf(wave_xor_sum(sq) / C + eps);
     const bool live = !keep_row || keep_row[row] != 0;
     if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
 #pragma unroll
@@ -131,12 +79,12 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const T* __restrict__ x
         if (c < C) {
             const long i = row * C + c;
             float gm[V], bt[V], o[V];
-            nm_ldv<V>(gamma, c, gm);
-            nm_ldv<V>(beta, c, bt);
+            el_ldv<V>(gamma, c, gm);
+            el_ldv<V>(beta, c, bt);
 #pragma unroll
             for (int q = 0; q < V; ++q) o[q] = live ? (v[jj][q] - mean) * rstd * gm[q] + bt[q] : 0.f;
-            nm_stv<V>(v_out, i, v[jj]);
-            nm_stv<V>(y, i, o);
+            el_stv<V>(v_out, i, v[jj]);
+            el_stv<V>(y, i, o);
         }
     }
 }
@@ -191,10 +139,10 @@ __global__ __launch_bounds__(256) void fc_add_ln_fwd_kernel(const unsigned short
     float r[NT][4], bs[NT][4], gm[NT][4], bt[NT][4];
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
-        nm_ldv<4>(res, rl * C + cc[i], r[i]);
-        nm_ldv<4>(bias, cc[i], bs[i]);
-        nm_ldv<4>(gamma, cc[i], gm[i]);
-        nm_ldv<4>(beta, cc[i], bt[i]);
+        el_ldv<4>(res, rl * C + cc[i], r[i]);
+        el_ldv<4>(bias, cc[i], bs[i]);
+        el_ldv<4>(gamma, cc[i], gm[i]);
+        el_ldv<4>(beta, cc[i], bt[i]);
     }
     const bool live = !keep_row || keep_row[rl] != 0;
     f32x4 acc[NT];
@@ -264,8 +212,8 @@ __global__ __launch_bounds__(256) void fc_add_ln_fwd_kernel(const unsigned short
             float o[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) o[q] = live ? (v[i][q] - mean) * rstd * gm[i][q] + bt[i][q] : 0.f;
-            nm_stv<4>(v_out, e0, v[i]);
-            nm_stv<4>(y, e0, o);
+            el_stv<4>(v_out, e0, v[i]);
+            el_stv<4>(y, e0, o);
         }
     }
 }
@@ -297,7 +245,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const T* __restrict__ g
         const int c = (lane + 64 * jj) * V;
 #pragma unroll
         for (int q = 0; q < V; ++q) dg[jj][q] = dbt[jj][q] = gm[jj][q] = 0.f;
-        if (c < C) nm_ldv<V>(gamma, c, gm[jj]);
+        if (c < C) el_ldv<V>(gamma, c, gm[jj]);
     }
     const long r0 = (long)blockIdx.x * rows_per_block;
     long rend = r0 + rows_per_block;
@@ -319,8 +267,8 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const T* __restrict__ g
 #pragma unroll
                 for (int q = 0; q < V; ++q) dx[u][jj][q] = xh[u][jj][q] = 0.f;
                 if (has && c < C) {
-                    nm_ldv<V>(g, row * C + c, dx[u][jj]);
-                    nm_ldv<V>(v_in, row * C + c, xh[u][jj]);
+                    el_ldv<V>(g, row * C + c, dx[u][jj]);
+                    el_ldv<V>(v_in, row * C + c, xh[u][jj]);
                 }
             }
         }
@@ -347,7 +295,7 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const T* __restrict__ g
                     }
                 }
             }
-            const float m1 = nm_wave_sum(s1) / C, m2 = nm_wave_sum(s2) / C;
+            const float m1 = wave_xor_sum(s1) / C, m2 = wave_xor_sum(s2) / C;
 #pragma unroll
             for (int jj = 0; jj < NG; ++jj) {
                 const int c = (lane + 64 * jj) * V;
@@ -360,8 +308,8 @@ __global__ __launch_bounds__(256) void add_ln_bwd_kernel(const T* __restrict__ g
                         d[q] = dv[q];
                         if (thresh) d[q] = nm_keep(key, (unsigned long long)(i + q), thresh) ? dv[q] * scale : 0.f;
                     }
-                    if (gres) nm_stv<V>(gres, i, dv);
-                    nm_stv<V>(gx, i, d);
+                    if (gres) el_stv<V>(gres, i, dv);
+                    el_stv<V>(gx, i, d);
                 }
             }
         }
@@ -437,10 +385,10 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const T* __restrict__ x, 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long n = i / C;
         const int c = (int)(i - n * C);
-        const float a = nm_ld(x, n * 2 * C + c), b = nm_ld(x, n * 2 * C + C + c);
+        const float a = el_ld(x, n * 2 * C + c), b = el_ld(x, n * 2 * C + C + c);
         float v = tanhf(a) * (1.f / (1.f + expf(-b)));
         if (thresh) v = nm_keep(key, (unsigned long long)i, thresh) ? v * scale : 0.f;
-        nm_st(y, i, v);
+        el_st(y, i, v);
     }
 }
 template <typename T>
@@ -453,24 +401,24 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const T* __restrict__ x, 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long n = i / C;
         const int c = (int)(i - n * C);
-        const float a = nm_ld(x, n * 2 * C + c), b = nm_ld(x, n * 2 * C + C + c);
-        float gv = nm_ld(g, i);
+        const float a = el_ld(x, n * 2 * C + c), b = el_ld(x, n * 2 * C + C + c);
+        float gv = el_ld(g, i);
         if (thresh) gv = nm_keep(key, (unsigned long long)i, thresh) ? gv * scale : 0.f;
         const float t = tanhf(a), s = 1.f / (1.f + expf(-b));
-        nm_st(gx, n * 2 * C + c, gv * s * (1.f - t * t));
-        nm_st(gx, n * 2 * C + C + c, gv * t * s * (1.f - s));
+        el_st(gx, n * 2 * C + c, gv * s * (1.f - t * t));
+        el_st(gx, n * 2 * C + C + c, gv * t * s * (1.f - s));
     }
 }
 // y = tanh(x);  gx = g * (1 - y*y)   (n elements)
 template <typename T>
 __global__ __launch_bounds__(256) void tanh_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) nm_st(y, i, tanhf(nm_ld(x, i)));
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) el_st(y, i, tanhf(el_ld(x, i)));
 }
 template <typename T>
 __global__ __launch_bounds__(256) void tanh_bwd_kernel(const T* __restrict__ y, const T* __restrict__ g, T* __restrict__ gx, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float t = nm_ld(y, i);
-        nm_st(gx, i, nm_ld(g, i) * (1.f - t * t));
+        const float t = el_ld(y, i);
+        el_st(gx, i, el_ld(g, i) * (1.f - t * t));
     }
 }
 
@@ -478,13 +426,13 @@ __global__ __launch_bounds__(256) void tanh_bwd_kernel(const T* __restrict__ y, 
 // last convolution in, fp32 out -- cast + tanh were two launches forward and two backward (the gradient leaves in the compute dtype)
 template <typename T>
 __global__ __launch_bounds__(256) void tanh_f32_fwd_kernel(const T* __restrict__ x, float* __restrict__ y, long n) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = tanhf(nm_ld(x, i));
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = tanhf(el_ld(x, i));
 }
 template <typename T>
 __global__ __launch_bounds__(256) void tanh_f32_bwd_kernel(const float* __restrict__ y, const float* __restrict__ g, T* __restrict__ gx, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const float t = y[i];
-        nm_st(gx, i, g[i] * (1.f - t * t));
+        el_st(gx, i, g[i] * (1.f - t * t));
     }
 }
 
@@ -500,17 +448,17 @@ __global__ __launch_bounds__(256) void sum_n_kernel(const T* __restrict__ a, con
                                                     const T* __restrict__ d, T* __restrict__ out, long n4) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         float va[4], vb[4], vc[4], vd[4], o[4];
-        nm_ldv<4>(a, 4 * i, va);
-        nm_ldv<4>(b, 4 * i, vb);
-        if (c) nm_ldv<4>(c, 4 * i, vc);
-        if (d) nm_ldv<4>(d, 4 * i, vd);
+        el_ldv<4>(a, 4 * i, va);
+        el_ldv<4>(b, 4 * i, vb);
+        if (c) el_ldv<4>(c, 4 * i, vc);
+        if (d) el_ldv<4>(d, 4 * i, vd);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             o[q] = va[q] + vb[q];
             if (c) o[q] = o[q] + vc[q];
             if (d) o[q] = o[q] + vd[q];
         }
-        nm_stv<4>(out, 4 * i, o);
+        el_stv<4>(out, 4 * i, o);
     }
 }
 template <typename T, bool BWD>
@@ -521,14 +469,14 @@ __global__ __launch_bounds__(256) void dropout_add_kernel(const T* __restrict__ 
     const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         float v[4], r[4];
-        nm_ldv<4>(x, 4 * i, v);
-        if (!BWD && res) nm_ldv<4>(res, 4 * i, r);
+        el_ldv<4>(x, 4 * i, v);
+        if (!BWD && res) el_ldv<4>(res, 4 * i, r);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (thresh) v[q] = nm_keep(key, (unsigned long long)(4 * i + q), thresh) ? v[q] * scale : 0.f;
             if (!BWD && res) v[q] = v[q] + r[q];
         }
-        nm_stv<4>(y, 4 * i, v);
+        el_stv<4>(y, 4 * i, v);
     }
 }
 template <typename T>
@@ -537,7 +485,7 @@ __global__ __launch_bounds__(256) void row_mask_kernel(const void* __restrict__ 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int b = (int)(i / Tn), t = (int)(i - (long)b * Tn);
         const long len = is64 ? (long)((const long long*)lengths)[b] : (long)((const int*)lengths)[b];
-        nm_st(keep, i, t < len ? 1.f : 0.f);
+        el_st(keep, i, t < len ? 1.f : 0.f);
     }
 }
 
@@ -563,11 +511,11 @@ __global__ __launch_bounds__(256) void fft_prologue_kernel(const TI* __restrict_
     const float* trow = table + (size_t)(live ? t + 1 : 0) * C;
     for (int c = lane * V; c < C; c += 64 * V) {
         float a[V], e[V], o[V];
-        nm_ldv<V>(seq, row * C + c, a);
-        nm_ldv<V>(trow, c, e);
+        el_ldv<V>(seq, row * C + c, a);
+        el_ldv<V>(trow, c, e);
 #pragma unroll
         for (int q = 0; q < V; ++q) o[q] = a[q] + e[q];
-        nm_stv<V>(out, row * C + c, o);
+        el_stv<V>(out, row * C + c, o);
     }
     const float ninf = -__builtin_huge_valf();
     if (lane == 0) {
@@ -606,7 +554,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const long r = row + (long)u * l.R;
-                bn_ld(x, (r < r1 ? r : r1 - 1) * C + l.cg * V, v[u]);
+                el_ldv(x, (r < r1 ? r : r1 - 1) * C + l.cg * V, v[u]);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -639,8 +587,8 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
 #pragma unroll
             for (int q = 0; q < V; ++q) bn_chan(cnt[q], mean[q], m2[q], nb, s_mean[j * C + l.cg * V + q], s_m2[j * C + l.cg * V + q]);
         }
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.cg * V, mean);
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.cg * V, m2);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.cg * V, mean);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.cg * V, m2);
         if (threadIdx.x == 0) ((int*)(ws + (long)nblk * 2 * C))[blockIdx.x] = (int)(r1 - r0);
     }
 }
@@ -667,8 +615,8 @@ __global__ __launch_bounds__(256) void bn_norm_kernel(const T* __restrict__ x, c
             const int* counts = (const int*)(ws + (long)nblk * 2 * C);
             for (int j = l.rr; j < nblk; j += l.R) {
                 float mb[V], m2b[V];
-                bn_ld<V>(ws, ((long)j * 2 + 0) * C + l.cg * V, mb);
-                bn_ld<V>(ws, ((long)j * 2 + 1) * C + l.cg * V, m2b);
+                el_ldv<V>(ws, ((long)j * 2 + 0) * C + l.cg * V, mb);
+                el_ldv<V>(ws, ((long)j * 2 + 1) * C + l.cg * V, m2b);
                 const float nb = (float)counts[j];
 #pragma unroll
                 for (int q = 0; q < V; ++q) bn_chan(cnt[q], mean[q], m2[q], nb, mb[q], m2b[q]);
@@ -718,10 +666,10 @@ __global__ __launch_bounds__(256) void bn_norm_kernel(const T* __restrict__ x, c
 #pragma unroll 4
     for (long row = r0 + l.rr; row < r1; row += l.R) {
         float v[V];
-        bn_ld(x, row * C + l.cg * V, v);
+        el_ldv(x, row * C + l.cg * V, v);
 #pragma unroll
         for (int q = 0; q < V; ++q) v[q] = (v[q] - mean[q]) * rstd[q];
-        bn_st(y, row * C + l.cg * V, v);
+        el_stv(y, row * C + l.cg * V, v);
     }
 }
 
@@ -739,13 +687,13 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const TG* __restrict_
     for (int q = 0; q < V; ++q) s1[q] = s2[q] = 0.f;
     if (l.rr < l.R) {
         float mean[V], rstd[V];
-        bn_ld<V>(mean_in, l.cg * V, mean);
-        bn_ld<V>(rstd_in, l.cg * V, rstd);
+        el_ldv<V>(mean_in, l.cg * V, mean);
+        el_ldv<V>(rstd_in, l.cg * V, rstd);
 #pragma unroll 4
         for (long row = r0 + l.rr; row < r1; row += l.R) {
             float v[V], gv[V];
-            bn_ld(x, row * C + l.cg * V, v);
-            bn_ld(g, row * C + l.cg * V, gv);
+            el_ldv(x, row * C + l.cg * V, v);
+            el_ldv(g, row * C + l.cg * V, gv);
 #pragma unroll
             for (int q = 0; q < V; ++q) {
                 s1[q] = s1[q] + gv[q];
@@ -766,8 +714,8 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_kernel(const TG* __restrict_
                 s1[q] = s1[q] + s_1[j * C + l.cg * V + q];
                 s2[q] = s2[q] + s_2[j * C + l.cg * V + q];
             }
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.cg * V, s1);
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.cg * V, s2);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.cg * V, s1);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.cg * V, s2);
     }
 }
 
@@ -786,8 +734,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const TG* __restrict_
     if (l.rr < l.R) {
         for (int j = l.rr; j < nblk; j += l.R) {
             float a[V], b[V];
-            bn_ld<V>(ws, ((long)j * 2 + 0) * C + l.cg * V, a);
-            bn_ld<V>(ws, ((long)j * 2 + 1) * C + l.cg * V, b);
+            el_ldv<V>(ws, ((long)j * 2 + 0) * C + l.cg * V, a);
+            el_ldv<V>(ws, ((long)j * 2 + 1) * C + l.cg * V, b);
 #pragma unroll
             for (int q = 0; q < V; ++q) { s1[q] = s1[q] + a[q]; s2[q] = s2[q] + b[q]; }
         }
@@ -808,19 +756,19 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const TG* __restrict_
             s2[q] = s2[q] + s_2[j * C + l.cg * V + q];
         }
     float mean[V], rstd[V];
-    bn_ld<V>(mean_in, l.cg * V, mean);
-    bn_ld<V>(rstd_in, l.cg * V, rstd);
+    el_ldv<V>(mean_in, l.cg * V, mean);
+    el_ldv<V>(rstd_in, l.cg * V, rstd);
 #pragma unroll
     for (int q = 0; q < V; ++q) { s1[q] = s1[q] / (float)N; s2[q] = s2[q] / (float)N; }
     const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
 #pragma unroll 4
     for (long row = r0 + l.rr; row < r1; row += l.R) {
         float v[V], gv[V];
-        bn_ld(x, row * C + l.cg * V, v);
-        bn_ld(g, row * C + l.cg * V, gv);
+        el_ldv(x, row * C + l.cg * V, v);
+        el_ldv(g, row * C + l.cg * V, gv);
 #pragma unroll
         for (int q = 0; q < V; ++q) v[q] = rstd[q] * ((gv[q] - s1[q]) - ((v[q] - mean[q]) * rstd[q]) * s2[q]);
-        bn_st(gx, row * C + l.cg * V, v);
+        el_stv(gx, row * C + l.cg * V, v);
     }
 }
 
@@ -832,15 +780,15 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const TG* __restrict__
     const bn_lanes l = bn_geometry<V>(C);
     if (l.rr >= l.R) return;
     float rstd[V];
-    bn_ld<V>(rstd_in, l.cg * V, rstd);
+    el_ldv<V>(rstd_in, l.cg * V, rstd);
     const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
 #pragma unroll 4
     for (long row = r0 + l.rr; row < r1; row += l.R) {
         float gv[V];
-        bn_ld(g, row * C + l.cg * V, gv);
+        el_ldv(g, row * C + l.cg * V, gv);
 #pragma unroll
         for (int q = 0; q < V; ++q) gv[q] = gv[q] * rstd[q];
-        bn_st(gx, row * C + l.cg * V, gv);
+        el_stv(gx, row * C + l.cg * V, gv);
     }
 }
 
@@ -863,9 +811,13 @@ int msmc_add_ln_fwd(const void* x, const void* res, const float* gamma, const fl
     MSMC_LAUNCH((add_ln_fwd_kernel<T_, V_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const T_*)res, gamma, \
                 beta, keep_row, (T_*)y, (T_*)v, mean, rstd, N, C, eps, p_drop, seed, salt)
     const bool vec = (C % 4) == 0;          // rows start 8 / 16-byte aligned: vector accesses
-    if (dtype == 0) { if (vec) NM_FWD(float, 4); else NM_FWD(float, 1); }
-    else if (dtype == 1) { if (vec) NM_FWD(unsigned short, 4); else NM_FWD(unsigned short, 1); }
-    else return MSMC_E_SHAPE;
+#define NM_FWD_GO(T_)                                                                                                   \
+    do {                                                                                                                \
+        if (vec) NM_FWD(T_, 4);                                                                                         \
+        else NM_FWD(T_, 1);                                                                                             \
+    } while (0)
+    MSMC_BY_DTYPE(dtype, NM_FWD_GO);
+#undef NM_FWD_GO
 #undef NM_FWD
     return msmc_check_launch();
 }
@@ -917,18 +869,17 @@ int msmc_add_ln_bwd(const void* g, const void* v, const float* mean, const float
 #define NM_BWD(T_, V_, NG_, RW_)                                                                                        \
     MSMC_LAUNCH((add_ln_bwd_kernel<T_, V_, NG_, RW_>), dim3((unsigned)nblocks), dim3(256), lds, (msmc_stream_t)stream, (const T_*)g, \
                 (const T_*)v, mean, rstd, gamma, keep_row, (T_*)gx, (T_*)gres, (float*)workspace, N, C, p_drop, seed, salt, rows)
-#define NM_BWD_VEC(T_)                                                                                                  \
+#define NM_BWD_GO(T_)                                                                                                   \
     do {                                                                                                                \
-        if (C <= 256) NM_BWD(T_, 4, 1, 1);                                                                              \
+        if (!vec) NM_BWD(T_, 1, 16, 1);                                                                                 \
+        else if (C <= 256) NM_BWD(T_, 4, 1, 1);                                                                         \
         else if (C <= 512) NM_BWD(T_, 4, 2, 1);                                                                         \
         else if (C <= 768) NM_BWD(T_, 4, 3, 1);                                                                         \
         else NM_BWD(T_, 4, 4, 1);                                                                                       \
     } while (0)
         const bool vec = (C % 4) == 0;
-        if (dtype == 0) { if (vec) NM_BWD_VEC(float); else NM_BWD(float, 1, 16, 1); }
-        else if (dtype == 1) { if (vec) NM_BWD_VEC(unsigned short); else NM_BWD(unsigned short, 1, 16, 1); }
-        else return MSMC_E_SHAPE;
-#undef NM_BWD_VEC
+        MSMC_BY_DTYPE(dtype, NM_BWD_GO);
+#undef NM_BWD_GO
 #undef NM_BWD
         int rc = msmc_check_launch();
         if (rc) return rc;
@@ -984,9 +935,9 @@ int msmc_gate_fwd(const void* x, void* y, long N, int C, float p_drop, const lon
     if (!x || !y || N < 0 || C <= 0 || p_drop < 0.f || p_drop >= 1.f) return MSMC_E_SHAPE;
     if (N == 0) return 0;
     const dim3 grid((unsigned)nm_grid(N * C));
-    if (dtype == 0) MSMC_LAUNCH(gate_fwd_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)x, (float*)y, N, C, p_drop, seed, salt);
-    else if (dtype == 1) MSMC_LAUNCH(gate_fwd_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)x, (unsigned short*)y, N, C, p_drop, seed, salt);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(gate_fwd_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (T_*)y, N, C, p_drop, seed, salt)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_gate_bwd(const void* x, const void* g, void* gx, long N, int C, float p_drop, const long long* seed, long long salt,
@@ -994,84 +945,84 @@ int msmc_gate_bwd(const void* x, const void* g, void* gx, long N, int C, float p
     if (!x || !g || !gx || N < 0 || C <= 0) return MSMC_E_SHAPE;
     if (N == 0) return 0;
     const dim3 grid((unsigned)nm_grid(N * C));
-    if (dtype == 0) MSMC_LAUNCH(gate_bwd_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)x, (const float*)g, (float*)gx, N, C, p_drop, seed, salt);
-    else if (dtype == 1) MSMC_LAUNCH(gate_bwd_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)x, (const unsigned short*)g, (unsigned short*)gx, N, C, p_drop, seed, salt);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(gate_bwd_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const T_*)g, (T_*)gx, N, C, p_drop, seed, salt)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_tanh_fwd(const void* x, void* y, long n, int dtype, msmc_stream stream) {
     if (!x || !y || n < 0) return MSMC_E_SHAPE;
     if (n == 0) return 0;
     const dim3 grid((unsigned)nm_grid(n));
-    if (dtype == 0) MSMC_LAUNCH(tanh_fwd_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)x, (float*)y, n);
-    else if (dtype == 1) MSMC_LAUNCH(tanh_fwd_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)x, (unsigned short*)y, n);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(tanh_fwd_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (T_*)y, n)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_tanh_f32_fwd(const void* x, float* y, long n, int dtype, msmc_stream stream) {
     if (!x || !y || n < 0) return MSMC_E_SHAPE;
     if (n == 0) return 0;
     const dim3 grid((unsigned)nm_grid(n));
-    if (dtype == 0) MSMC_LAUNCH(tanh_f32_fwd_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)x, y, n);
-    else if (dtype == 1) MSMC_LAUNCH(tanh_f32_fwd_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)x, y, n);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(tanh_f32_fwd_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, y, n)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_tanh_f32_bwd(const float* y, const float* g, void* gx, long n, int dtype, msmc_stream stream) {
     if (!y || !g || !gx || n < 0) return MSMC_E_SHAPE;
     if (n == 0) return 0;
     const dim3 grid((unsigned)nm_grid(n));
-    if (dtype == 0) MSMC_LAUNCH(tanh_f32_bwd_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, y, g, (float*)gx, n);
-    else if (dtype == 1) MSMC_LAUNCH(tanh_f32_bwd_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, y, g, (unsigned short*)gx, n);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(tanh_f32_bwd_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, y, g, (T_*)gx, n)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_sum_n(const void* a, const void* b, const void* c, const void* d, void* out, long n, int dtype, msmc_stream stream) {
     if (!a || !b || !out || n < 0 || (n & 3) || (d && !c)) return MSMC_E_SHAPE;
-    if ((((size_t)a) | ((size_t)b) | ((size_t)c) | ((size_t)d) | ((size_t)out)) & (dtype == 0 ? 15 : 7)) return MSMC_E_SHAPE;
+    if (!msmc_aligned4(((size_t)a) | ((size_t)b) | ((size_t)c) | ((size_t)d) | ((size_t)out), dtype)) return MSMC_E_SHAPE;
     if (n == 0) return 0;
     const dim3 grid((unsigned)nm_grid(n / 4));
-    if (dtype == 0) MSMC_LAUNCH(sum_n_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)a, (const float*)b, (const float*)c, (const float*)d, (float*)out, n / 4);
-    else if (dtype == 1) MSMC_LAUNCH(sum_n_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)a, (const unsigned short*)b, (const unsigned short*)c, (const unsigned short*)d, (unsigned short*)out, n / 4);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(sum_n_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)a, (const T_*)b, (const T_*)c, (const T_*)d, (T_*)out, n / 4)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_dropout_add_fwd(const void* x, const void* res, void* y, long n, float p_drop, const long long* seed, long long salt, int dtype,
                          msmc_stream stream) {
     if (!x || !y || n < 0 || (n & 3) || p_drop < 0.f || p_drop >= 1.f) return MSMC_E_SHAPE;
-    if ((((size_t)x) | ((size_t)res) | ((size_t)y)) & (dtype == 0 ? 15 : 7)) return MSMC_E_SHAPE;
+    if (!msmc_aligned4(((size_t)x) | ((size_t)res) | ((size_t)y), dtype)) return MSMC_E_SHAPE;
     if (n == 0) return 0;
     const dim3 grid((unsigned)nm_grid(n / 4));
-    if (dtype == 0) MSMC_LAUNCH((dropout_add_kernel<float, false>), grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)x, (const float*)res, (float*)y, n / 4, p_drop, seed, salt);
-    else if (dtype == 1) MSMC_LAUNCH((dropout_add_kernel<unsigned short, false>), grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)x, (const unsigned short*)res, (unsigned short*)y, n / 4, p_drop, seed, salt);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH((dropout_add_kernel<T_, false>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const T_*)res, (T_*)y, n / 4, p_drop, seed, salt)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_dropout_bwd(const void* g, void* gx, long n, float p_drop, const long long* seed, long long salt, int dtype, msmc_stream stream) {
     if (!g || !gx || n < 0 || (n & 3) || p_drop < 0.f || p_drop >= 1.f) return MSMC_E_SHAPE;
-    if ((((size_t)g) | ((size_t)gx)) & (dtype == 0 ? 15 : 7)) return MSMC_E_SHAPE;
+    if (!msmc_aligned4(((size_t)g) | ((size_t)gx), dtype)) return MSMC_E_SHAPE;
     if (n == 0) return 0;
     const dim3 grid((unsigned)nm_grid(n / 4));
-    if (dtype == 0) MSMC_LAUNCH((dropout_add_kernel<float, true>), grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)g, (const float*)nullptr, (float*)gx, n / 4, p_drop, seed, salt);
-    else if (dtype == 1) MSMC_LAUNCH((dropout_add_kernel<unsigned short, true>), grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)g, (const unsigned short*)nullptr, (unsigned short*)gx, n / 4, p_drop, seed, salt);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH((dropout_add_kernel<T_, true>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)g, (const T_*)nullptr, (T_*)gx, n / 4, p_drop, seed, salt)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_row_mask(const void* lengths, int lengths_are_int64, void* keep, int B, int T, int dtype, msmc_stream stream) {
     if (!lengths || !keep || B <= 0 || T <= 0) return MSMC_E_SHAPE;
     const dim3 grid((unsigned)nm_grid((long)B * T));
-    if (dtype == 0) MSMC_LAUNCH(row_mask_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, lengths, lengths_are_int64, (float*)keep, B, T);
-    else if (dtype == 1) MSMC_LAUNCH(row_mask_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, lengths, lengths_are_int64, (unsigned short*)keep, B, T);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(row_mask_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, lengths, lengths_are_int64, (T_*)keep, B, T)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 int msmc_tanh_bwd(const void* y, const void* g, void* gx, long n, int dtype, msmc_stream stream) {
     if (!y || !g || !gx || n < 0) return MSMC_E_SHAPE;
     if (n == 0) return 0;
     const dim3 grid((unsigned)nm_grid(n));
-    if (dtype == 0) MSMC_LAUNCH(tanh_bwd_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)y, (const float*)g, (float*)gx, n);
-    else if (dtype == 1) MSMC_LAUNCH(tanh_bwd_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)y, (const unsigned short*)g, (unsigned short*)gx, n);
-    else return MSMC_E_SHAPE;
+#define NM_GO(T_) MSMC_LAUNCH(tanh_bwd_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)y, (const T_*)g, (T_*)gx, n)
+    MSMC_BY_DTYPE(dtype, NM_GO);
+#undef NM_GO
     return msmc_check_launch();
 }
 
@@ -1101,9 +1052,7 @@ int msmc_bn_fwd(const void* x, void* y, float* mean, float* rstd, float* running
         MSMC_LAUNCH((bn_norm_kernel<T_, TO_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const float*)ws, gr.nblk, \
                     (TO_*)y, mean, rstd, running_mean, running_var, num_batches_tracked, N, C, gr.slab, eps, momentum);     \
     } while (0)
-    if (dtype == 0) BN_FWD(float, float);
-    else if (out_dtype == 0) BN_FWD(unsigned short, float);
-    else BN_FWD(unsigned short, unsigned short);
+    MSMC_BY_DTYPE2(dtype, out_dtype, BN_FWD);
 #undef BN_FWD
     return msmc_check_launch();
 }
@@ -1120,9 +1069,7 @@ int msmc_bn_eval_fwd(const void* x, const float* running_mean, const float* runn
     MSMC_LAUNCH((bn_norm_kernel<T_, TO_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const float*)nullptr, 0, \
                 (TO_*)y, (float*)nullptr, rstd, (float*)running_mean, (float*)running_var, (long long*)nullptr, N, C, gr.slab, \
                 eps, 0.f)
-    if (dtype == 0) BN_EVAL(float, float);
-    else if (out_dtype == 0) BN_EVAL(unsigned short, float);
-    else BN_EVAL(unsigned short, unsigned short);
+    MSMC_BY_DTYPE2(dtype, out_dtype, BN_EVAL);
 #undef BN_EVAL
     return msmc_check_launch();
 }
@@ -1145,9 +1092,7 @@ int msmc_bn_bwd(const void* g, const void* x, const float* mean, const float* rs
         MSMC_LAUNCH((bn_bwd_apply_kernel<T_, TG_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const TG_*)g, (const T_*)x, mean, \
                     rstd, (const float*)ws, gr.nblk, (T_*)gx, N, C, gr.slab);                                              \
     } while (0)
-    if (dtype == 0) BN_BWD(float, float);
-    else if (g_dtype == 0) BN_BWD(unsigned short, float);
-    else BN_BWD(unsigned short, unsigned short);
+    MSMC_BY_DTYPE2(dtype, g_dtype, BN_BWD);
 #undef BN_BWD
     return msmc_check_launch();
 }
@@ -1161,9 +1106,7 @@ int msmc_bn_eval_bwd(const void* g, const float* rstd, void* gx, long N, int C, 
     const dim3 grid((unsigned)gr.nblk);
 #define BN_EBWD(T_, TG_)                                                                                                   \
     MSMC_LAUNCH((bn_eval_bwd_kernel<T_, TG_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const TG_*)g, rstd, (T_*)gx, N, C, gr.slab)
-    if (dtype == 0) BN_EBWD(float, float);
-    else if (g_dtype == 0) BN_EBWD(unsigned short, float);
-    else BN_EBWD(unsigned short, unsigned short);
+    MSMC_BY_DTYPE2(dtype, g_dtype, BN_EBWD);
 #undef BN_EBWD
     return msmc_check_launch();
 }

@@ -8,6 +8,7 @@
 // replay from a hipGraph unchanged.  All arithmetic fp32; reductions in a fixed order (bit-reproducible).
 #include <msmc_rt.hpp>
 #include <msmc_hip.h>
+#include "elem.inc"
 
 #define OPT_CHUNK 4096          // elements per workgroup
 
@@ -18,18 +19,6 @@ MSMC_DEV int opt_find(const msmc_opt_tensor* t, int n, int blk) {
         if (t[mid].first_chunk <= blk) lo = mid; else hi = mid - 1;
     }
     return lo;
-}
-MSMC_DEV float opt_block_sum(float v, float* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
 }
 
 __global__ __launch_bounds__(256) void opt_gradsq_kernel(const msmc_opt_tensor* __restrict__ table, int nt,
@@ -55,7 +44,7 @@ __global__ __launch_bounds__(256) void opt_gradsq_kernel(const msmc_opt_tensor* 
             if (e < t.n) s = fmaf(t.g[e], t.g[e], s);
         }
     }
-    s = opt_block_sum(s, red);
+    s = block_tree_sum<true>(s, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -67,7 +56,7 @@ __global__ __launch_bounds__(256) void opt_norm_kernel(const float* __restrict__
     float s = 0.f;
     if (max_norm > 0.f)
         for (int k = threadIdx.x; k < nblocks; k += 256) s = s + partial[k];
-    s = opt_block_sum(s, red);
+    s = block_tree_sum<true>(s, red);
     if (threadIdx.x == 0) {
         const float norm = sqrtf(s);
         float coef = 1.f;

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void rbn_stats_kernel(const T* __restrict__ x,
 #pragma unroll 4
         for (long row = r0 + l.rr; row < r1; row += l.R) {
             float v[V];
-            bn_ld(x, row * ldx + l.c0, v);
+            el_ldv(x, row * ldx + l.c0, v);
             n = n + 1;
             const float inv = 1.f / (float)n;
 #pragma unroll
@@ -81,8 +81,8 @@ __global__ __launch_bounds__(256) void rbn_stats_kernel(const T* __restrict__ x,
 #pragma unroll
             for (int q = 0; q < V; ++q) bn_chan(cnt[q], mean[q], m2[q], nb, s_mean[TD_LDS_ROW(l, j, q)], s_m2[TD_LDS_ROW(l, j, q)]);
         }
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.c0, mean);
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.c0, m2);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.c0, mean);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.c0, m2);
         if (threadIdx.x == 0 && blockIdx.y == 0) ((int*)(ws + (long)nblk * 2 * C))[blockIdx.x] = (int)(r1 - r0);
     }
 }
@@ -110,8 +110,8 @@ __global__ __launch_bounds__(256) void rbn_norm_kernel(const T* __restrict__ x, 
             const int* counts = (const int*)(ws + (long)nblk * 2 * C);
             for (int j = l.rr; j < nblk; j += l.R) {
                 float mb[V], m2b[V];
-                bn_ld<V>(ws, ((long)j * 2 + 0) * C + l.c0, mb);
-                bn_ld<V>(ws, ((long)j * 2 + 1) * C + l.c0, m2b);
+                el_ldv<V>(ws, ((long)j * 2 + 0) * C + l.c0, mb);
+                el_ldv<V>(ws, ((long)j * 2 + 1) * C + l.c0, m2b);
                 const float nb = (float)counts[j];
 #pragma unroll
                 for (int q = 0; q < V; ++q) bn_chan(cnt[q], mean[q], m2[q], nb, mb[q], m2b[q]);
@@ -158,16 +158,16 @@ __global__ __launch_bounds__(256) void rbn_norm_kernel(const T* __restrict__ x, 
         }
     }
     float ga[V], be[V];
-    bn_ld<V>(gamma, l.c0, ga);
-    bn_ld<V>(beta, l.c0, be);
+    el_ldv<V>(gamma, l.c0, ga);
+    el_ldv<V>(beta, l.c0, be);
     const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
 #pragma unroll 4
     for (long row = r0 + l.rr; row < r1; row += l.R) {
         float v[V];
-        bn_ld(x, row * ldx + l.c0, v);
+        el_ldv(x, row * ldx + l.c0, v);
 #pragma unroll
         for (int q = 0; q < V; ++q) v[q] = (((v[q] > 0.f ? v[q] : 0.f) - mean[q]) * rstd[q]) * ga[q] + be[q];
-        bn_st(y, row * ldy + l.c0, v);
+        el_stv(y, row * ldy + l.c0, v);
     }
 }
 
@@ -185,13 +185,13 @@ __global__ __launch_bounds__(256) void rbn_bwd_stats_kernel(const T* __restrict_
     for (int q = 0; q < V; ++q) s1[q] = s2[q] = 0.f;
     if (l.live) {
         float mean[V], rstd[V];
-        bn_ld<V>(mean_in, l.c0, mean);
-        bn_ld<V>(rstd_in, l.c0, rstd);
+        el_ldv<V>(mean_in, l.c0, mean);
+        el_ldv<V>(rstd_in, l.c0, rstd);
 #pragma unroll 4
         for (long row = r0 + l.rr; row < r1; row += l.R) {
             float v[V], gv[V];
-            bn_ld(x, row * ldx + l.c0, v);
-            bn_ld(g, row * ldg + l.c0, gv);
+            el_ldv(x, row * ldx + l.c0, v);
+            el_ldv(g, row * ldg + l.c0, gv);
 #pragma unroll
             for (int q = 0; q < V; ++q) {
                 s1[q] = s1[q] + gv[q];
@@ -212,8 +212,8 @@ __global__ __launch_bounds__(256) void rbn_bwd_stats_kernel(const T* __restrict_
                 s1[q] = s1[q] + s_1[TD_LDS_ROW(l, j, q)];
                 s2[q] = s2[q] + s_2[TD_LDS_ROW(l, j, q)];
             }
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.c0, s1);
-        bn_st<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.c0, s2);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 0) * C + l.c0, s1);
+        el_stv<V>(ws, ((long)blockIdx.x * 2 + 1) * C + l.c0, s2);
     }
 }
 
@@ -236,8 +236,8 @@ __global__ __launch_bounds__(256) void rbn_bwd_apply_kernel(const T* __restrict_
         if (l.live) {
             for (int j = l.rr; j < nblk; j += l.R) {
                 float a[V], b[V];
-                bn_ld<V>(ws, ((long)j * 2 + 0) * C + l.c0, a);
-                bn_ld<V>(ws, ((long)j * 2 + 1) * C + l.c0, b);
+                el_ldv<V>(ws, ((long)j * 2 + 0) * C + l.c0, a);
+                el_ldv<V>(ws, ((long)j * 2 + 1) * C + l.c0, b);
 #pragma unroll
                 for (int q = 0; q < V; ++q) { s1[q] = s1[q] + a[q]; s2[q] = s2[q] + b[q]; }
             }
@@ -258,24 +258,24 @@ __global__ __launch_bounds__(256) void rbn_bwd_apply_kernel(const T* __restrict_
                 s2[q] = s2[q] + s_2[TD_LDS_ROW(l, j, q)];
             }
         if (blockIdx.x == 0 && l.rr == 0 && dgamma) {
-            bn_st<V>(dbeta, l.c0, s1);
-            bn_st<V>(dgamma, l.c0, s2);
+            el_stv<V>(dbeta, l.c0, s1);
+            el_stv<V>(dgamma, l.c0, s2);
         }
     } else if (!l.live) {
         return;
     }
     float mean[V], rstd[V], ga[V];
-    bn_ld<V>(mean_in, l.c0, mean);
-    bn_ld<V>(rstd_in, l.c0, rstd);
-    bn_ld<V>(gamma, l.c0, ga);
+    el_ldv<V>(mean_in, l.c0, mean);
+    el_ldv<V>(rstd_in, l.c0, rstd);
+    el_ldv<V>(gamma, l.c0, ga);
 #pragma unroll
     for (int q = 0; q < V; ++q) { s1[q] = s1[q] / (float)N; s2[q] = s2[q] / (float)N; }
     const long r0 = (long)blockIdx.x * slab, r1 = r0 + slab < N ? r0 + slab : N;
 #pragma unroll 4
     for (long row = r0 + l.rr; row < r1; row += l.R) {
         float v[V], gv[V];
-        bn_ld(x, row * ldx + l.c0, v);
-        bn_ld(g, row * ldg + l.c0, gv);
+        el_ldv(x, row * ldx + l.c0, v);
+        el_ldv(g, row * ldg + l.c0, gv);
 #pragma unroll
         for (int q = 0; q < V; ++q) {
             const float r = v[q] > 0.f ? v[q] : 0.f;
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void rbn_bwd_apply_kernel(const T* __restrict_
             else d = (ga[q] * rstd[q]) * ((gv[q] - s1[q]) - ((r - mean[q]) * rstd[q]) * s2[q]);
             v[q] = v[q] > 0.f ? d : 0.f;
         }
-        bn_st(gx, row * ldgx + l.c0, v);
+        el_stv(gx, row * ldgx + l.c0, v);
     }
 }
 
@@ -305,10 +305,10 @@ __global__ __launch_bounds__(256) void se_sums_kernel(const T* __restrict__ a, c
 #pragma unroll 4
         for (int row = r0 + l.rr; row < r1; row += l.R) {
             float v[V];
-            bn_ld(a, base + (long)row * C + l.c0, v);
+            el_ldv(a, base + (long)row * C + l.c0, v);
             if constexpr (MUL) {
                 float w[V];
-                bn_ld(b, base + (long)row * C + l.c0, w);
+                el_ldv(b, base + (long)row * C + l.c0, w);
 #pragma unroll
                 for (int q = 0; q < V; ++q) v[q] = v[q] * w[q];
             }
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void se_sums_kernel(const T* __restrict__ a, c
         for (int j = 1; j < l.R; ++j)
 #pragma unroll
             for (int q = 0; q < V; ++q) s[q] = s[q] + s_1[TD_LDS_ROW(l, j, q)];
-        bn_st<V>(ws, ((long)blockIdx.z * gridDim.x + blockIdx.x) * C + l.c0, s);
+        el_stv<V>(ws, ((long)blockIdx.z * gridDim.x + blockIdx.x) * C + l.c0, s);
     }
 }
 
@@ -384,16 +384,16 @@ __global__ __launch_bounds__(256) void se_scale_kernel(const T* __restrict__ a, 
     const long base = (long)blockIdx.z * Tn * C;
     const int r0 = (int)blockIdx.x * slab, r1 = r0 + slab < Tn ? r0 + slab : Tn;
     float gt[V], dv[V];
-    bn_ld<V>(gate, (long)blockIdx.z * C + l.c0, gt);
-    if constexpr (ROWVEC) bn_ld<V>((const float*)add, (long)blockIdx.z * C + l.c0, dv);
+    el_ldv<V>(gate, (long)blockIdx.z * C + l.c0, gt);
+    if constexpr (ROWVEC) el_ldv<V>((const float*)add, (long)blockIdx.z * C + l.c0, dv);
 #pragma unroll 4
     for (int row = r0 + l.rr; row < r1; row += l.R) {
         float v[V];
-        bn_ld(a, base + (long)row * C + l.c0, v);
-        if constexpr (!ROWVEC) bn_ld((const T*)add, base + (long)row * C + l.c0, dv);
+        el_ldv(a, base + (long)row * C + l.c0, v);
+        if constexpr (!ROWVEC) el_ldv((const T*)add, base + (long)row * C + l.c0, dv);
 #pragma unroll
         for (int q = 0; q < V; ++q) v[q] = v[q] * gt[q] + dv[q];
-        bn_st(y, base + (long)row * C + l.c0, v);
+        el_stv(y, base + (long)row * C + l.c0, v);
     }
 }
 
@@ -426,8 +426,8 @@ __global__ __launch_bounds__(256) void asp_part_kernel(const T* __restrict__ x, 
 #pragma unroll 2
         for (int row = r0 + l.rr; row < r1; row += l.R) {
             float xv[V], av[V];
-            bn_ld(x, base + (long)row * C + l.c0, xv);
-            bn_ld(a, base + (long)row * C + l.c0, av);
+            el_ldv(x, base + (long)row * C + l.c0, xv);
+            el_ldv(a, base + (long)row * C + l.c0, av);
 #pragma unroll
             for (int q = 0; q < V; ++q) {
                 // one exponential per element: the larger of (running maximum, new logit) keeps weight 1
@@ -456,10 +456,10 @@ __global__ __launch_bounds__(256) void asp_part_kernel(const T* __restrict__ x, 
                 asp_merge(m[q], ls[q], s1[q], s2[q], s_m[TD_LDS_ROW(l, j, q)], s_l[TD_LDS_ROW(l, j, q)], s_1[TD_LDS_ROW(l, j, q)],
                           s_2[TD_LDS_ROW(l, j, q)]);
         const long o = ((long)blockIdx.z * gridDim.x + blockIdx.x) * 4 * C + l.c0;
-        bn_st<V>(ws, o, m);
-        bn_st<V>(ws, o + C, ls);
-        bn_st<V>(ws, o + 2L * C, s1);
-        bn_st<V>(ws, o + 3L * C, s2);
+        el_stv<V>(ws, o, m);
+        el_stv<V>(ws, o + C, ls);
+        el_stv<V>(ws, o + 2L * C, s1);
+        el_stv<V>(ws, o + 3L * C, s2);
     }
 }
 
@@ -499,12 +499,12 @@ __global__ __launch_bounds__(256) void asp_bwd_kernel(const float* __restrict__ 
     {
         float ls[V], mean[V], res[V], gm[V], gs[V];
         const long s0 = (long)blockIdx.z * 4 * C + l.c0;
-        bn_ld<V>(stats, s0, m);
-        bn_ld<V>(stats, s0 + C, ls);
-        bn_ld<V>(stats, s0 + 2L * C, mean);
-        bn_ld<V>(stats, s0 + 3L * C, res);
-        bn_ld<V>(gout, (long)blockIdx.z * 2 * C + l.c0, gm);
-        bn_ld<V>(gout, (long)blockIdx.z * 2 * C + C + l.c0, gs);
+        el_ldv<V>(stats, s0, m);
+        el_ldv<V>(stats, s0 + C, ls);
+        el_ldv<V>(stats, s0 + 2L * C, mean);
+        el_ldv<V>(stats, s0 + 3L * C, res);
+        el_ldv<V>(gout, (long)blockIdx.z * 2 * C + l.c0, gm);
+        el_ldv<V>(gout, (long)blockIdx.z * 2 * C + C + l.c0, gs);
 #pragma unroll
         for (int q = 0; q < V; ++q) {
             const float dres = res[q] < 1e-9f ? 0.f : gs[q] / (2.f * sqrtf(res[q]));
@@ -517,8 +517,8 @@ __global__ __launch_bounds__(256) void asp_bwd_kernel(const float* __restrict__ 
 #pragma unroll 2
     for (int row = r0 + l.rr; row < r1; row += l.R) {
         float xv[V], av[V];
-        bn_ld(x, base + (long)row * C + l.c0, xv);
-        bn_ld(a, base + (long)row * C + l.c0, av);
+        el_ldv(x, base + (long)row * C + l.c0, xv);
+        el_ldv(a, base + (long)row * C + l.c0, av);
 #pragma unroll
         for (int q = 0; q < V; ++q) {
             const float al = expf(av[q] - m[q]) * il[q];
@@ -526,8 +526,8 @@ __global__ __launch_bounds__(256) void asp_bwd_kernel(const float* __restrict__ 
             av[q] = al * ((k0[q] * xx + k1[q] * (xx * xx)) - dot[q]);
             xv[q] = al * (k0[q] + 2.f * k1[q] * xx);
         }
-        bn_st(gx, base + (long)row * C + l.c0, xv);
-        bn_st(ga, base + (long)row * C + l.c0, av);
+        el_stv(gx, base + (long)row * C + l.c0, xv);
+        el_stv(ga, base + (long)row * C + l.c0, av);
     }
 }
 
@@ -588,8 +588,7 @@ int msmc_relu_bn_fwd(const void* x, long ldx, const float* gamma, const float* b
                     gamma, beta, (T_*)y, ldy, mean, rstd, running_mean, running_var, num_batches_tracked, N, C, gr.slab, eps,   \
                     momentum);                                                                                               \
     } while (0)
-    if (dtype == 0) RBN_FWD(float);
-    else RBN_FWD(unsigned short);
+    MSMC_BY_DTYPE(dtype, RBN_FWD);
 #undef RBN_FWD
     return msmc_check_launch();
 }
@@ -607,8 +606,7 @@ int msmc_relu_bn_eval_fwd(const void* x, long ldx, const float* gamma, const flo
     MSMC_LAUNCH((rbn_norm_kernel<T_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, ldx, (const float*)nullptr, 0,   \
                 gamma, beta, (T_*)y, ldy, (float*)nullptr, rstd, (float*)running_mean, (float*)running_var, (long long*)nullptr, \
                 N, C, gr.slab, eps, 0.f)
-    if (dtype == 0) RBN_EVAL(float);
-    else RBN_EVAL(unsigned short);
+    MSMC_BY_DTYPE(dtype, RBN_EVAL);
 #undef RBN_EVAL
     return msmc_check_launch();
 }
@@ -634,8 +632,7 @@ int msmc_relu_bn_bwd(const void* g, long ldg, const void* x, long ldx, const flo
         MSMC_LAUNCH((rbn_bwd_apply_kernel<T_, false>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)g, ldg, (const T_*)x, \
                     ldx, mean, rstd, gamma, (const float*)ws, gr.nblk, (T_*)gx, ldgx, dgamma, dbeta, N, C, gr.slab);         \
     } while (0)
-    if (dtype == 0) RBN_BWD(float);
-    else RBN_BWD(unsigned short);
+    MSMC_BY_DTYPE(dtype, RBN_BWD);
 #undef RBN_BWD
     return msmc_check_launch();
 }
@@ -663,8 +660,7 @@ int msmc_relu_bn_eval_bwd(const void* g, long ldg, const void* x, long ldx, cons
         MSMC_LAUNCH((rbn_bwd_apply_kernel<T_, true>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)g, ldg, (const T_*)x, \
                     ldx, running_mean, rstd, gamma, (const float*)ws, gr.nblk, (T_*)gx, ldgx, dgamma, dbeta, N, C, gr.slab); \
     } while (0)
-    if (dtype == 0) RBN_EBWD(float);
-    else RBN_EBWD(unsigned short);
+    MSMC_BY_DTYPE(dtype, RBN_EBWD);
 #undef RBN_EBWD
     return msmc_check_launch();
 }
@@ -698,8 +694,7 @@ int msmc_se_fwd(const void* x, const void* res, const float* W1, const float* b1
         MSMC_LAUNCH((se_scale_kernel<T_, false>), dim3((unsigned)gs.nblk, (unsigned)nch, (unsigned)B), dim3(256), 0,         \
                     (msmc_stream_t)stream, (const T_*)x, (const float*)gate, res, (T_*)y, T, C, (int)gs.slab);                \
     } while (0)
-    if (dtype == 0) SE_FWD(float);
-    else SE_FWD(unsigned short);
+    MSMC_BY_DTYPE(dtype, SE_FWD);
 #undef SE_FWD
     return msmc_check_launch();
 }
@@ -715,8 +710,7 @@ int msmc_se_bwd_gate(const void* g, const void* x, float* dgate, void* workspace
 #define SE_BG(T_)                                                                                                            \
     MSMC_LAUNCH((se_sums_kernel<T_, true>), dim3((unsigned)gr.nblk, (unsigned)nch, (unsigned)B), dim3(256), 0,               \
                 (msmc_stream_t)stream, (const T_*)g, (const T_*)x, ws, T, C, (int)gr.slab)
-    if (dtype == 0) SE_BG(float);
-    else SE_BG(unsigned short);
+    MSMC_BY_DTYPE(dtype, SE_BG);
 #undef SE_BG
     int rc = msmc_check_launch();
     if (rc) return rc;
@@ -734,8 +728,7 @@ int msmc_se_bwd_apply(const void* g, const float* gate, const float* dmean, void
 #define SE_BA(T_)                                                                                                            \
     MSMC_LAUNCH((se_scale_kernel<T_, true>), dim3((unsigned)gs.nblk, (unsigned)nch, (unsigned)B), dim3(256), 0,              \
                 (msmc_stream_t)stream, (const T_*)g, gate, (const void*)dmean, (T_*)gx, T, C, (int)gs.slab)
-    if (dtype == 0) SE_BA(float);
-    else SE_BA(unsigned short);
+    MSMC_BY_DTYPE(dtype, SE_BA);
 #undef SE_BA
     return msmc_check_launch();
 }
@@ -757,8 +750,7 @@ int msmc_asp_fwd(const void* x, const void* a, float* out, float* stats, void* w
 #define ASP_FWD(T_)                                                                                                          \
     MSMC_LAUNCH((asp_part_kernel<T_>), dim3((unsigned)gr.nblk, (unsigned)nch, (unsigned)B), dim3(256), 0, (msmc_stream_t)stream, \
                 (const T_*)x, (const T_*)a, ws, T, C, (int)gr.slab)
-    if (dtype == 0) ASP_FWD(float);
-    else ASP_FWD(unsigned short);
+    MSMC_BY_DTYPE(dtype, ASP_FWD);
 #undef ASP_FWD
     int rc = msmc_check_launch();
     if (rc) return rc;
@@ -776,8 +768,7 @@ int msmc_asp_bwd(const float* gout, const void* x, const void* a, const float* s
 #define ASP_BWD(T_)                                                                                                          \
     MSMC_LAUNCH((asp_bwd_kernel<T_>), dim3((unsigned)gs.nblk, (unsigned)nch, (unsigned)B), dim3(256), 0, (msmc_stream_t)stream, \
                 gout, (const T_*)x, (const T_*)a, stats, (T_*)gx, (T_*)ga, T, C, (int)gs.slab)
-    if (dtype == 0) ASP_BWD(float);
-    else ASP_BWD(unsigned short);
+    MSMC_BY_DTYPE(dtype, ASP_BWD);
 #undef ASP_BWD
     return msmc_check_launch();
 }

@@ -13,6 +13,7 @@
 // increasing utterance indices); with duplicates the LAST entry naming an utterance wins, still within bounds.
 #include <msmc_rt.hpp>
 #include <msmc_hip.h>
+#include "elem.inc"
 
 // V consecutive elements (V = 8: 16-byte aligned) from src[si..] in its dtype to dst[di..] in its dtype; !valid: zeros
 template <int SBF, int DBF, int V>
@@ -22,9 +23,9 @@ MSMC_DEV void wg_copy(const void* __restrict__ src, long si, void* __restrict__ 
             if (SBF) ((unsigned short*)dst)[di] = valid ? ((const unsigned short*)src)[si] : (unsigned short)0;
             else ((unsigned int*)dst)[di] = valid ? ((const unsigned int*)src)[si] : 0u;
         } else if (SBF) {
-            ((float*)dst)[di] = valid ? bf16_bits_to_f32(((const unsigned short*)src)[si]) : 0.f;
+            el_st((float*)dst + di, valid ? el_ld((const unsigned short*)src + si) : 0.f);
         } else {
-            ((unsigned short*)dst)[di] = valid ? f32_to_bf16_bits(((const float*)src)[si]) : (unsigned short)0;
+            el_st((unsigned short*)dst + di, valid ? el_ld((const float*)src + si) : 0.f);
         }
         return;
     }

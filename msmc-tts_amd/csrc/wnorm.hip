@@ -8,19 +8,6 @@
 // ================================================================================================
 // weight norm (multi-tensor) and bias gradient
 // ================================================================================================
-MSMC_DEV float block_sum(float v, float* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    float r = red[0];
-    __syncthreads();
-    return r;
-}
-
 MSMC_DEV int wn_find(const msmc_wn_item* items, int n, int blk) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
@@ -30,15 +17,9 @@ MSMC_DEV int wn_find(const msmc_wn_item* items, int n, int blk) {
     return lo;
 }
 
-MSMC_DEV void wn_store(void* dst, int dtype, long off, float v) {
-    if (dtype == 0) ((float*)dst)[off] = v;
-    else ((unsigned short*)dst)[off] = f32_to_bf16_bits(v);
-}
-
 // sum over the 256 work-items of a workgroup: wave reduction by lane exchange, then four partial sums through LDS
 MSMC_DEV float block_sum_fast(float v, float* red4) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + wave_xor(v, m);
+    v = wave_xor_sum(v);
     const int w = threadIdx.x >> 6;
     __syncthreads();                                   // (red4 may still be read from a previous call)
     if ((threadIdx.x & 63) == 0) red4[w] = v;
@@ -48,8 +29,7 @@ MSMC_DEV float block_sum_fast(float v, float* red4) {
 
 // the same for workgroups of one to four waves (blockDim.x / 64)
 MSMC_DEV float block_sum_waves(float v, float* red4) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + wave_xor(v, m);
+    v = wave_xor_sum(v);
     const int w = threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red4[w] = v;
@@ -163,7 +143,7 @@ __global__ __launch_bounds__(256) void wn_transpose_kernel(const msmc_wn_item* _
         const float sc = lane < na ? scl[lane] : 0.f;
         for (int c = w; c < nc; c += 4) {
             if (lane < na)
-                wn_store(it.dst2, it.dtype, t * it.s2[0] + (a0 + lane) * it.s2[1] + (b0 + b) * it.s2[2], tile[lane * pitch + c] * sc);
+                el_st_rt(it.dst2, it.dtype, t * it.s2[0] + (a0 + lane) * it.s2[1] + (b0 + b) * it.s2[2], tile[lane * pitch + c] * sc);
             t += 4;
             while (t >= T) { t -= T; ++b; }
         }
@@ -293,7 +273,7 @@ __global__ __launch_bounds__(256) void wn_layout_kernel(const msmc_wn_item* __re
             const float sc = al < na ? scl[al] : 0.f;
             for (; c < ncol; c += step) {
                 if (al < na)
-                    wn_store(it.dst2, it.dtype, t * it.s2[0] + (a0 + al) * it.s2[1] + (b0 + b) * it.s2[2], tile[al * pitch + c] * sc);
+                    el_st_rt(it.dst2, it.dtype, t * it.s2[0] + (a0 + al) * it.s2[1] + (b0 + b) * it.s2[2], tile[al * pitch + c] * sc);
                 b += qs;
                 t += rs;
                 if (t >= T) { t -= T; ++b; }
@@ -327,7 +307,7 @@ __global__ __launch_bounds__(256) void wn_layout_kernel(const msmc_wn_item* __re
             const float sc = scl[a];
             const long o = t * it.s1[0] + (a0 + a) * it.s1[1] + (long)b0 * it.s1[2];
             const float* row = tile + a * pitch + t;
-            for (int bb = bl; bb < nb; bb += lpr) wn_store(it.dst1, it.dtype, o + bb * it.s1[2], row[bb * T] * sc);
+            for (int bb = bl; bb < nb; bb += lpr) el_st_rt(it.dst1, it.dtype, o + bb * it.s1[2], row[bb * T] * sc);
         }
     }
 }
@@ -888,14 +868,11 @@ int msmc_reflect_fold(const void* gp, const void* mask_src, void* gx, int B, int
     const long total = (long)B * H * W * C;
     long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    if (dtype == 0)
-        MSMC_LAUNCH(reflect_fold_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (msmc_stream_t)stream,
-                    (const float*)gp, (const float*)mask_src, (float*)gx, B, H, W, C, p, slope, total);
-    else if (dtype == 1)
-        MSMC_LAUNCH(reflect_fold_kernel<unsigned short>, dim3((unsigned)blocks), dim3(256), 0, (msmc_stream_t)stream,
-                    (const unsigned short*)gp, (const unsigned short*)mask_src, (unsigned short*)gx, B, H, W, C, p,
-                    slope, total);
-    else return MSMC_E_SHAPE;
+#define WN_GO(T_)                                                                                                   \
+    MSMC_LAUNCH(reflect_fold_kernel<T_>, dim3((unsigned)blocks), dim3(256), 0, (msmc_stream_t)stream, (const T_*)gp,     \
+                (const T_*)mask_src, (T_*)gx, B, H, W, C, p, slope, total)
+    MSMC_BY_DTYPE(dtype, WN_GO);
+#undef WN_GO
     return msmc_check_launch();
 }
 
@@ -903,13 +880,11 @@ int msmc_lrelu_bwd(const void* g, const void* y, void* gx, long n, float slope, 
     if (!g || !y || !gx || n <= 0) return MSMC_E_SHAPE;
     long blocks = (n + 1023) / 1024;
     if (blocks > 2048) blocks = 2048;
-    if (dtype == 0)
-        MSMC_LAUNCH(lrelu_bwd_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (msmc_stream_t)stream,
-                    (const float*)g, (const float*)y, (float*)gx, n, slope);
-    else if (dtype == 1)
-        MSMC_LAUNCH(lrelu_bwd_kernel<unsigned short>, dim3((unsigned)blocks), dim3(256), 0, (msmc_stream_t)stream,
-                    (const unsigned short*)g, (const unsigned short*)y, (unsigned short*)gx, n, slope);
-    else return MSMC_E_SHAPE;
+#define WN_GO(T_)                                                                                                   \
+    MSMC_LAUNCH(lrelu_bwd_kernel<T_>, dim3((unsigned)blocks), dim3(256), 0, (msmc_stream_t)stream, (const T_*)g,         \
+                (const T_*)y, (T_*)gx, n, slope)
+    MSMC_BY_DTYPE(dtype, WN_GO);
+#undef WN_GO
     return msmc_check_launch();
 }
 
@@ -947,9 +922,9 @@ int msmc_colsum_ws(const void* g, float* out, long rows, int C, int dtype, int a
     const int nb = colsum_blocks(rows);
     const int rpb = (int)((rows + nb - 1) / nb);
     float* part = (float*)workspace;
-    if (dtype == 0) MSMC_LAUNCH(colsum_part_kernel<float>, dim3(nb), dim3(256), 0, (msmc_stream_t)stream, (const float*)g, part, rows, C, rpb);
-    else if (dtype == 1) MSMC_LAUNCH(colsum_part_kernel<unsigned short>, dim3(nb), dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)g, part, rows, C, rpb);
-    else return MSMC_E_SHAPE;
+#define WN_GO(T_) MSMC_LAUNCH(colsum_part_kernel<T_>, dim3(nb), dim3(256), 0, (msmc_stream_t)stream, (const T_*)g, part, rows, C, rpb)
+    MSMC_BY_DTYPE(dtype, WN_GO);
+#undef WN_GO
     int rc = msmc_check_launch();
     if (rc) return rc;
     const int used = (int)((rows + rpb - 1) / rpb);  // (blocks that own rows)
@@ -1034,9 +1009,9 @@ int msmc_colsum(const void* g, float* out, long rows, int C, int dtype, msmc_str
     int rpb = 256;
     while ((rows + rpb - 1) / rpb > 4096) rpb <<= 1;
     dim3 grid((unsigned)((rows + rpb - 1) / rpb));
-    if (dtype == 0) MSMC_LAUNCH(colsum_kernel<float>, grid, dim3(256), 0, (msmc_stream_t)stream, (const float*)g, out, rows, C, rpb);
-    else if (dtype == 1) MSMC_LAUNCH(colsum_kernel<unsigned short>, grid, dim3(256), 0, (msmc_stream_t)stream, (const unsigned short*)g, out, rows, C, rpb);
-    else return MSMC_E_SHAPE;
+#define WN_GO(T_) MSMC_LAUNCH(colsum_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)g, out, rows, C, rpb)
+    MSMC_BY_DTYPE(dtype, WN_GO);
+#undef WN_GO
     return msmc_check_launch();
 }
 

@@ -264,7 +264,7 @@ def check_norm_kernels(dev, dtype, tol):
     row mask; dropout: the backward pass regenerates exactly the forward's mask and the keep rate is right"""
     from msmctts_amd.hip import norm
     torch.manual_seed(0)
-    for N, C in ((37, 256), (5, 96), (130, 32)):
+    def add_ln_case(N, C, report=None):
         x = torch.randn(N, C, device=dev).to(dtype).requires_grad_(True)
         r = torch.randn(N, C, device=dev).to(dtype).requires_grad_(True)
         gm = (torch.rand(C, device=dev) + 0.5).requires_grad_(True)
@@ -278,11 +278,20 @@ def check_norm_kernels(dev, dtype, tol):
         yr = torch.nn.functional.layer_norm(xr + rr, (C,), gr, br) * keep.float().unsqueeze(1)
         (yr * (go.to(dtype).float() if dtype != torch.float32 else go)).sum().backward()
         scale = lambda t: max(1.0, float(t.abs().max()))
+        if report:
+            print('%s N=%d C=%d %s: y %.3e / %.3e  gx %.3e / %.3e  gres %.3e / %.3e  dgamma %.3e / %.3e  dbeta %.3e / %.3e (error / bound)' % (
+                report, N, C, dtype, float((y.float() - yr).abs().max()), tol * scale(yr),
+                float((x.grad.float() - xr.grad).abs().max()), tol * scale(xr.grad),
+                float((r.grad.float() - rr.grad).abs().max()), tol * scale(rr.grad),
+                float((gm.grad - gr.grad).abs().max()), tol * scale(gr.grad) * (4 if dtype != torch.float32 else 1),
+                float((bt.grad - br.grad).abs().max()), tol * scale(br.grad) * (4 if dtype != torch.float32 else 1)))
         assert (y.float() - yr).abs().max() <= tol * scale(yr)
         assert (x.grad.float() - xr.grad).abs().max() <= tol * scale(xr.grad)
         assert (r.grad.float() - rr.grad).abs().max() <= tol * scale(rr.grad)
         assert (gm.grad - gr.grad).abs().max() <= tol * scale(gr.grad) * (4 if dtype != torch.float32 else 1)
         assert (bt.grad - br.grad).abs().max() <= tol * scale(br.grad) * (4 if dtype != torch.float32 else 1)
+    for N, C in ((37, 256), (5, 96), (130, 32)):
+        add_ln_case(N, C)
     # gate and tanh
     x = torch.randn(23, 2 * 48, device=dev).to(dtype).requires_grad_(True)
     y = norm.gate(x)
@@ -313,6 +322,10 @@ def check_norm_kernels(dev, dtype, tol):
     norm.advance_seed(xg.device)
     y2 = norm.gate(xg.detach(), p_drop=p, salt=salt)
     assert not torch.equal(y2 != 0, y != 0)
+    # narrow rows, last so that the cases above keep their random inputs: C = 6 is no multiple of 4 (one element per access,
+    # V = 1), C = 8 the narrowest row of the vector path (V = 4); tolerances as above
+    for N, C in ((5, 6), (5, 8)):
+        add_ln_case(N, C, report='add-LayerNorm narrow')
 
 
 def check_fc_add_ln(dev):
@@ -1359,6 +1372,21 @@ def check_masked_mean_and_colsum(dev):
         K.colsum(g, out=acc)
         close(acc, want + 1.0, 1e-4 * max(1.0, float(want.abs().max())), what='colsum accumulate')
         assert torch.equal(K.colsum(g), K.colsum(g))                  # fixed summation order
+    # mode 1 with an fp32 prediction against a bf16 target (the mixed-type element loads), lengths (7, 3)
+    B, T, C = 2, 7, 5
+    lengths = torch.tensor([7, 3], device=dev)
+    pad = get_mask_from_lengths(lengths, T).unsqueeze(-1)
+    a = torch.randn(B, T, C, device=dev, requires_grad=True)
+    b = torch.randn(B, T, C, device=dev).to(torch.bfloat16).requires_grad_(True)
+    want = F.mse_loss(b.float(), a, reduction='none').masked_fill(pad, 0).sum() / lengths.sum() / C
+    gwa, gwb = torch.autograd.grad(want, (a, b))
+    got = losses.masked_mean(a, lengths, b=b)
+    gga, ggb = torch.autograd.grad(got, (a, b))
+    assert gga.dtype == torch.float32 and ggb.dtype == torch.bfloat16
+    close(got, want, 1e-5, what='masked mse fp32 / bf16')
+    close(gga, gwa, 1e-6, what='masked mse fp32 / bf16 grad a')
+    close(ggb, gwb, 2e-3 * float(gwb.float().abs().max()), what='masked mse fp32 / bf16 grad b')
+    assert float(gga[1, 3:].abs().sum()) == 0.0 and float(ggb.float()[1, 3:].abs().sum()) == 0.0
 
 
 def check_gan_loss_kernels(dev):
@@ -1397,6 +1425,27 @@ def check_gan_loss_kernels(dev):
         close(got, want, tol, what='l1 sum (offset view)')
         (ga,), (gb,) = torch.autograd.grad(got, base), torch.autograd.grad(want, base)
         close(ga, gb, tol * max(1e-3, float(gb.float().abs().max())) if dt == torch.bfloat16 else 1e-7, what='l1 grad (offset view)')
+    # a table of two tensors of 8 * 256 + 3 elements: from element 0 of their buffers (16-byte aligned: vector body and a
+    # 3-element tail) and from element 1 (misaligned: every element on the scalar path); last, so that the cases above keep
+    # their random inputs
+    n = 8 * 256 + 3
+    for dt, tol in ((torch.float32, 1e-5), (torch.bfloat16, 1e-2)):
+        for off in (0, 1):
+            fbuf = [torch.randn(n + 8, device=dev).to(dt).requires_grad_(True) for _ in range(2)]
+            rbuf = [torch.randn(n + 8, device=dev).to(dt) for _ in range(2)]
+            fake, real = [t[off:off + n] for t in fbuf], [t[off:off + n] for t in rbuf]
+            assert all((t.data_ptr() % 16 == 0) == (off == 0) for t in fake + real)
+            gtol = lambda g: tol * max(1e-3, float(g.float().abs().max()))
+            got = losses.l1_sum(fake, real)
+            want = sum(F.l1_loss(a.float(), b.float()) for a, b in zip(fake, real))
+            close(got, want, tol, what='l1 sum (n = 2051, offset %d)' % off)
+            for a, b in zip(torch.autograd.grad(got * 2.0, fbuf), torch.autograd.grad(want * 2.0, fbuf)):
+                close(a, b, gtol(b) if dt == torch.bfloat16 else 1e-7, what='l1 grad (n = 2051, offset %d)' % off)
+            got = losses.mse_const_sum(fake, 1.0)
+            want = sum(((a.float() - 1.0) ** 2).mean() for a in fake)
+            close(got, want, tol, what='mse const sum (n = 2051, offset %d)' % off)
+            for a, b in zip(torch.autograd.grad(got, fbuf), torch.autograd.grad(want, fbuf)):
+                close(a, b, gtol(b) if dt == torch.bfloat16 else 1e-6, what='mse grad (n = 2051, offset %d)' % off)
 
 
 def check_split_constant_gemm(dev):
