@@ -453,7 +453,9 @@ int msmc_colsum_ws(const void* g, float* out, long rows, int C, int dtype, int a
  * ------------------------------------------------------------------------------------------- */
 
 /* frames[b][t][j] = x[b][reflect(t*hop + j - pad)] for j < n_fft, 0 for n_fft <= j < NP (row pitch NP).
- * pad = n_fft/2 (centred STFT) or (n_fft-hop)/2 (MelLoss); x [B][L], frames [B][T][NP]. */
+ * pad = n_fft/2 (centred STFT) or (n_fft-hop)/2 (MelLoss); x [B][L], frames [B][T][NP].  The reflection folds once on each
+ * side: both entries (and kinds 0 / 1 of msmc_spectral_multi) return MSMC_E_SHAPE unless L > pad and the last position read,
+ * (T-1)*hop + n_fft - 1 - pad, is at most 2L - 2. */
 int msmc_stft_frames_fwd(const float* x, float* frames, int B, int L, int T, int n_fft, int NP, int hop, int pad,
                          msmc_stream stream);
 /* overlap-add adjoint: gx[b][l] = sum of gframes over every (t, j) that read sample l (reflections included). */

@@ -432,11 +432,19 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const long* __restri
     }
 }
 
+// Operands of the framing pair (and of kinds 0 / 1 of msmc_spectral_multi): sp_reflect folds an index once, so the last padded
+// position a frame reads, (T-1)*hop + n_fft - 1 - pad, must not pass the single right reflection's end 2L - 2 (L > pad keeps the
+// left one inside).
+static inline bool sp_frames_ok(int B, int L, int T, int n_fft, int NP, int hop, int pad) {
+    if (B <= 0 || L <= pad || T <= 0 || NP < n_fft || hop <= 0 || pad < 0) return false;
+    return (long)(T - 1) * hop + n_fft - 1 - pad <= 2 * (long)L - 2;
+}
+
 extern "C" {
 
 int msmc_stft_frames_fwd(const float* x, float* frames, int B, int L, int T, int n_fft, int NP, int hop, int pad,
                          msmc_stream stream) {
-    if (!x || !frames || B <= 0 || L <= pad || T <= 0 || NP < n_fft || hop <= 0 || pad < 0) return MSMC_E_SHAPE;
+    if (!x || !frames || !sp_frames_ok(B, L, T, n_fft, NP, hop, pad)) return MSMC_E_SHAPE;
     const long total = (long)B * T * NP;
     MSMC_LAUNCH(stft_frames_fwd_kernel, sp_grid(total), dim3(256), 0, (msmc_stream_t)stream, x, frames, L, T, n_fft, NP,
                 hop, pad, total);
@@ -444,7 +452,7 @@ int msmc_stft_frames_fwd(const float* x, float* frames, int B, int L, int T, int
 }
 int msmc_stft_frames_bwd(const float* gframes, float* gx, int B, int L, int T, int n_fft, int NP, int hop, int pad,
                          msmc_stream stream) {
-    if (!gframes || !gx || B <= 0 || L <= pad || T <= 0 || NP < n_fft || hop <= 0 || pad < 0) return MSMC_E_SHAPE;
+    if (!gframes || !gx || !sp_frames_ok(B, L, T, n_fft, NP, hop, pad)) return MSMC_E_SHAPE;
     const long total = (long)B * L;
     MSMC_LAUNCH(stft_frames_bwd_kernel, sp_grid(total), dim3(256), 0, (msmc_stream_t)stream, gframes, gx, L, T, n_fft, NP,
                 hop, pad, total);
@@ -585,7 +593,7 @@ int msmc_spectral_multi(const msmc_spectral_op* ops, int n, msmc_stream stream) 
         if (!o.a || !o.out) return MSMC_E_SHAPE;
         switch (o.kind) {
             case 0: case 1:
-                if (o.B <= 0 || o.L <= o.pad || o.T <= 0 || o.NP < o.n_fft || o.hop <= 0 || o.pad < 0) return MSMC_E_SHAPE;
+                if (!sp_frames_ok(o.B, o.L, o.T, o.n_fft, o.NP, o.hop, o.pad)) return MSMC_E_SHAPE;
                 total = o.kind == 0 ? (long)o.B * o.T * o.NP : (long)o.B * o.L;
                 break;
             case 2: case 3:
