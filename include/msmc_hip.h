@@ -635,7 +635,9 @@ int msmc_triple_loss_wide(const float* p, const int64_t* trg, const float* embed
  * p_drop == 0.  C <= 1024.
  * ------------------------------------------------------------------------------------------- */
 /* v = drop(x) + res (res may be NULL); y = LayerNorm(v) * gamma + beta, rows with keep_row[n] == 0 zeroed (keep_row may be
- * NULL); v, mean [N], rstd [N] are kept for the backward pass. */
+ * NULL); v, mean [N], rstd [N] are kept for the backward pass.  Any contiguous rows are taken: four-element vector accesses
+ * where C % 4 == 0 and x / res / y / v are 16-byte (fp32) / 8-byte (bf16) and gamma / beta 16-byte aligned, element accesses
+ * otherwise.  MSMC_E_SHAPE for C > 1024 or p_drop outside [0, 1). */
 int msmc_add_ln_fwd(const void* x, const void* res, const float* gamma, const float* beta, const unsigned char* keep_row,
                     void* y, void* v, float* mean, float* rstd, long N, int C, float eps, float p_drop,
                     const long long* seed, long long salt, int dtype, msmc_stream stream);
@@ -650,7 +652,9 @@ int msmc_fc_add_ln_fwd(const void* a, const void* W, const float* bias, const vo
 size_t msmc_add_ln_bwd_workspace(long N, int C);
 /* gx = d/dx, gres = d/dres (may be NULL), dgamma / dbeta fp32 [C] (accumulate != 0: +=), fixed reduction order.
  * dgamma == dbeta == NULL: only the per-workgroup partials are produced -- they stay in `workspace`
- * ([ceil(N / 16)][2][C] fp32, which the caller then keeps) for msmc_add_ln_param_multi. */
+ * ([ceil(N / 16)][2][C] fp32, which the caller then keeps) for msmc_add_ln_param_multi.  Alignment as msmc_add_ln_fwd (g / v / gx /
+ * gres and gamma: the element path where one of them does not start on a four-element boundary).  MSMC_E_SHAPE for C > 1024 or
+ * p_drop outside [0, 1), as the forward entry; MSMC_E_WORKSPACE below msmc_add_ln_bwd_workspace. */
 int msmc_add_ln_bwd(const void* g, const void* v, const float* mean, const float* rstd, const float* gamma,
                     const unsigned char* keep_row, void* gx, void* gres, float* dgamma, float* dbeta, void* workspace,
                     size_t workspace_bytes, long N, int C, float p_drop, const long long* seed, long long salt, int accumulate,
@@ -675,11 +679,14 @@ int msmc_add_ln_param_multi(const msmc_ln_param_item* items, int nitems, msmc_st
 /* Head of FFTBlocks.forward (reference msmctts/networks/acoustic_models/transformer.py:375-395) with the positions of
  * vqgantts/msmc_vqgan.py:56-58 folded in: out[b][t][:] = seq[b][t][:] + table[t < len[b] ? t + 1 : 0][:] (seq / out
  * [B][T][C] in in_dtype / out_dtype, table fp32 [table_rows][C], T + 1 <= table_rows), keep_row[b T + t] = t < len[b],
- * key_bias (may be NULL) [B][Tp] = 0 on real frames, -inf on padding and on the tail T .. Tp - 1.  lengths: int32 or int64. */
+ * key_bias (may be NULL) [B][Tp] = 0 on real frames, -inf on padding and on the tail T .. Tp - 1 (T <= Tp < T + 64: MSMC_E_SHAPE
+ * otherwise).  lengths: int32 or int64.  Vector accesses where C % 4 == 0 and seq / out / table start on a four-element boundary
+ * of their dtype (table: 16 bytes), element accesses otherwise. */
 int msmc_fft_prologue(const void* seq, const void* lengths, int len_is_64, const float* table, int table_rows, void* out,
                       unsigned char* keep_row, float* key_bias, int B, int T, int C, int Tp, int in_dtype, int out_dtype,
                       msmc_stream stream);
-/* x [N][2C] -> y [N][C] = drop(tanh(x[:, :C]) * sigmoid(x[:, C:])); backward recomputes from x. */
+/* x [N][2C] -> y [N][C] = drop(tanh(x[:, :C]) * sigmoid(x[:, C:])); backward recomputes from x.  Both entries: MSMC_E_SHAPE for
+ * p_drop outside [0, 1). */
 int msmc_gate_fwd(const void* x, void* y, long N, int C, float p_drop, const long long* seed, long long salt, int dtype,
                   msmc_stream stream);
 int msmc_gate_bwd(const void* x, const void* g, void* gx, long N, int C, float p_drop, const long long* seed, long long salt,

@@ -27,7 +27,8 @@ MSMC_DEV unsigned long long nm_key(const long long* seed, long long salt) {
 #define NM_MAXE 16          // elements per lane: C <= 1024
 
 // one wave per row: v = drop(x) + res; y = (v - mean) * rstd * gamma + beta, zeroed where keep_row == 0.
-// A lane owns the V-element groups (lane + 64 jj) * V .. + V of its row (V = 4 when C % 4 == 0: vector accesses).
+// A lane owns the V-element groups (lane + 64 jj) * V .. + V of its row (V = 4 when C % 4 == 0 and the operands are aligned to
+// four elements: vector accesses; V = 1 otherwise).
 template <typename T, int V>
 __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -522,7 +523,7 @@ __global__ __launch_bounds__(256) void fft_prologue_kernel(const TI* __restrict_
         keep_row[row] = live ? 1 : 0;
         if (key_bias) key_bias[(size_t)b * Tp + t] = live ? 0.f : ninf;
     }
-    if (key_bias && t == T - 1 && lane < Tp - T) key_bias[(size_t)b * Tp + T + lane] = ninf;      // (Tp - T < 32)
+    if (key_bias && t == T - 1 && lane < Tp - T) key_bias[(size_t)b * Tp + T + lane] = ninf;      // (Tp - T < 64: one lane each)
 }
 
 // ---- BatchNorm over frames (the normalised quantiser) -----------------------------------------------------------
@@ -810,7 +811,10 @@ int msmc_add_ln_fwd(const void* x, const void* res, const float* gamma, const fl
 #define NM_FWD(T_, V_)                                                                                                  \
     MSMC_LAUNCH((add_ln_fwd_kernel<T_, V_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const T_*)res, gamma, \
                 beta, keep_row, (T_*)y, (T_*)v, mean, rstd, N, C, eps, p_drop, seed, salt)
-    const bool vec = (C % 4) == 0;          // rows start 8 / 16-byte aligned: vector accesses
+    // vector accesses where every row of x / res / y / v starts 8 (bf16) / 16 (fp32) bytes aligned and gamma / beta 16 bytes: a
+    // contiguous view that begins inside a larger buffer takes the element path (it covers every C up to 1024)
+    const bool vec = (C % 4) == 0 && msmc_aligned4(((size_t)x) | ((size_t)res) | ((size_t)y) | ((size_t)v), dtype) &&
+                     msmc_aligned4(((size_t)gamma) | ((size_t)beta), 0);
 #define NM_FWD_GO(T_)                                                                                                   \
     do {                                                                                                                \
         if (vec) NM_FWD(T_, 4);                                                                                         \
@@ -860,7 +864,9 @@ int msmc_add_ln_bwd(const void* g, const void* v, const float* mean, const float
                     const unsigned char* keep_row, void* gx, void* gres, float* dgamma, float* dbeta, void* workspace,
                     size_t workspace_bytes, long N, int C, float p_drop, const long long* seed, long long salt, int accumulate,
                     int dtype, msmc_stream stream) {
-    if (!g || !v || !mean || !rstd || !gamma || !gx || (!dgamma != !dbeta) || N < 0 || C <= 0 || C > 64 * NM_MAXE) return MSMC_E_SHAPE;
+    if (!g || !v || !mean || !rstd || !gamma || !gx || (!dgamma != !dbeta) || N < 0 || C <= 0 || C > 64 * NM_MAXE || p_drop < 0.f ||
+        p_drop >= 1.f)
+        return MSMC_E_SHAPE;
     const int rows = NM_BWD_ROWS;
     const int nblocks = (int)((N + rows - 1) / rows);
     if (workspace_bytes < msmc_add_ln_bwd_workspace(N, C) || (nblocks && !workspace)) return MSMC_E_WORKSPACE;
@@ -877,7 +883,9 @@ int msmc_add_ln_bwd(const void* g, const void* v, const float* mean, const float
         else if (C <= 768) NM_BWD(T_, 4, 3, 1);                                                                         \
         else NM_BWD(T_, 4, 4, 1);                                                                                       \
     } while (0)
-        const bool vec = (C % 4) == 0;
+        // (as msmc_add_ln_fwd: the element path for rows or a gamma that do not start on a four-element boundary)
+        const bool vec = (C % 4) == 0 && msmc_aligned4(((size_t)g) | ((size_t)v) | ((size_t)gx) | ((size_t)gres), dtype) &&
+                         msmc_aligned4((size_t)gamma, 0);
         MSMC_BY_DTYPE(dtype, NM_BWD_GO);
 #undef NM_BWD_GO
 #undef NM_BWD
@@ -921,7 +929,8 @@ int msmc_fft_prologue(const void* seq, const void* lengths, int len_is_64, const
 #define NM_PRO(TI_, TO_, V_)                                                                                           \
     MSMC_LAUNCH((fft_prologue_kernel<TI_, TO_, V_>), grid, dim3(256), 0, (msmc_stream_t)stream, (const TI_*)seq, lengths, \
                 len_is_64, table, (TO_*)out, keep_row, key_bias, B, T, C, Tp)
-    const bool vec = (C % 4) == 0;
+    const bool vec = (C % 4) == 0 && msmc_aligned4((size_t)seq, in_dtype) && msmc_aligned4((size_t)out, out_dtype) &&
+                     msmc_aligned4((size_t)table, 0);
     if (in_dtype == 0 && out_dtype == 0) { if (vec) NM_PRO(float, float, 4); else NM_PRO(float, float, 1); }
     else if (in_dtype == 0) { if (vec) NM_PRO(float, unsigned short, 4); else NM_PRO(float, unsigned short, 1); }
     else if (out_dtype == 0) { if (vec) NM_PRO(unsigned short, float, 4); else NM_PRO(unsigned short, float, 1); }
@@ -942,7 +951,7 @@ int msmc_gate_fwd(const void* x, void* y, long N, int C, float p_drop, const lon
 }
 int msmc_gate_bwd(const void* x, const void* g, void* gx, long N, int C, float p_drop, const long long* seed, long long salt,
                   int dtype, msmc_stream stream) {
-    if (!x || !g || !gx || N < 0 || C <= 0) return MSMC_E_SHAPE;
+    if (!x || !g || !gx || N < 0 || C <= 0 || p_drop < 0.f || p_drop >= 1.f) return MSMC_E_SHAPE;
     if (N == 0) return 0;
     const dim3 grid((unsigned)nm_grid(N * C));
 #define NM_GO(T_) MSMC_LAUNCH(gate_bwd_kernel<T_>, grid, dim3(256), 0, (msmc_stream_t)stream, (const T_*)x, (const T_*)g, (T_*)gx, N, C, p_drop, seed, salt)
