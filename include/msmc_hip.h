@@ -83,6 +83,20 @@ int msmc_vq_search_stream(const float* x, const float* embed_t, const float* eno
 int msmc_vq_search_wide(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff,
                         int64_t* ind, int N, int d, int K, msmc_stream stream);
 
+/* The labels of that search and nothing else (msmc-tts_amd/csrc/vq_assign.inc): unit extraction over a corpus wants 8 bytes
+ * per frame, not quant and diff.  Operands as msmc_vq_search_wide; the search is the same code in the same instantiation
+ * (msmc_vq_wide_set_split included), so ind [N] is what msmc_vq_search_wide writes for these inputs, bit for bit (first
+ * minimum on ties).  dist [N] (may be NULL: then only ind is written) is the squared distance to the winner's row e =
+ * embed_t[ind[n]], recomputed as direct fp32 differences -- 0 exactly for a frame that equals its centroid, never the
+ * expanded form -- in a fixed order that does not depend on the split: the 16-byte pieces c4 = 0 .. d / 4 - 1 of the row go to
+ * 16 partial sums, piece c4 to partial c4 % 16; partial[p] = (((+0 + s_0) + s_1) + ...) over (x - e)^2 of the pieces p, p + 16,
+ * ... in ascending order and of the four channels of a piece in order; dist[n] = (((+0 + partial[0]) + partial[1]) + ... +
+ * partial[15]).  One rounding per difference, product and add.  No atomics.
+ * Takes d % 16 == 0, 16 <= d <= 2048, K >= 1, N >= 0 with N * d * 4 < 2^32, x and embed_t 16-byte aligned (MSMC_E_SHAPE
+ * otherwise, nothing launched); 0 at once for N == 0. */
+int msmc_vq_assign_wide(const float* x, const float* embed_t, const float* enorm, int64_t* ind, float* dist, int N, int d,
+                        int K, msmc_stream stream);
+
 /* The same search -- identical indices, quant and diff, bit for bit -- under the HBM roof for K >= 64
  * (msmc-tts_amd/csrc/vq_shortlist.inc): all K distances approximately on the bf16 matrix cores (two-piece bf16 splits of
  * x and e, three products), a running top-2 per frame, and a rigorous error bound that decides per (frame, head) whether
@@ -180,6 +194,27 @@ size_t msmc_kmeanspp_workspace(int N, int d, int K, int L);
  * MSMC_E_WORKSPACE for a workspace below msmc_kmeanspp_workspace. */
 int msmc_kmeanspp_seed(const float* x, int N, int d, int K, int L, long first, const double* u, float* centers, int64_t* chosen,
                        double* potential, void* workspace, size_t workspace_bytes, msmc_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * UN  from labels to units (msmc-tts_amd/csrc/units.hip; the labels: msmc_vq_assign_wide; host side msmctts_amd/hip/units.py).
+ * The reference counts code usage on the host with a dictionary (examples/qs-tts/scripts/vq_analysis.py
+ * compute_codebook_complexity) and has no run collapse.  Integer work: both results are exact.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Run-length collapse of the valid prefix ind[b][0 .. min(length[b], T)) of every utterance, ind [B][T], length [B]: maximal
+ * runs of equal labels, run r -> units[b][r] (the label), dur[b][r] (its frames), ulen[b] = the number of runs; the slots
+ * r >= ulen[b] get units = -1 and dur = 0.  units [B][T], dur [B][T], ulen [B]: every element is written exactly once, nothing
+ * at or beyond length[b] is read, length[b] <= 0 gives ulen[b] = 0.  One workgroup per utterance, any T.
+ * B <= 0 or T <= 0: MSMC_E_SHAPE. */
+int msmc_units_collapse(const int64_t* ind, const int64_t* length, int64_t* units, int32_t* dur, int64_t* ulen, int B, int T,
+                        msmc_stream stream);
+
+/* counts[k] = the number of valid frames (t < min(length[b], T)) of ind [B][T] labelled k, counts [K] int64; labels outside
+ * [0, K) are skipped.  accumulate = 0 overwrites counts, accumulate = 1 adds onto what it holds (a corpus, batch by batch).
+ * Integer adds only (LDS counters per workgroup, then 64-bit adds in global memory): exact in any order.
+ * B <= 0, T <= 0 or K <= 0: MSMC_E_SHAPE. */
+int msmc_units_usage(const int64_t* ind, const int64_t* length, int64_t* counts, int B, int T, int K, int accumulate,
+                     msmc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * G1/G2/D1/D2 channels-last implicit-GEMM convolution family on the matrix cores.

@@ -11,7 +11,8 @@
 // formed in LDS in place and written back with full-row stores.
 // Algorithmic HBM bytes per frame: 4D (x) + 4D (quant) + 8H (ind) + 4D/H (diff).
 //
-// One wide head (d up to 2048, any K: k-means unit codebooks) takes the GEMM-shaped kernel of vq_wide.inc (msmc_vq_search_wide).
+// One wide head (d up to 2048, any K: k-means unit codebooks) takes the GEMM-shaped kernel of vq_wide.inc (msmc_vq_search_wide);
+// vq_assign.inc runs the same search and stores the labels and the distance to the winner alone (msmc_vq_assign_wide).
 // Codebooks too large to stay resident (one head beyond 160 KiB of LDS) take the streamed kernel of vq_stream.inc: the same
 // pieces of vq_common.inc, hence the same bits, the codebook passing through LDS in double-buffered chunks.
 //
@@ -363,6 +364,7 @@ __global__ __launch_bounds__(256, 2) void vq_search_reg_kernel(const float* __re
 #include "vq_stream.inc"
 #include "wide_tile.inc"
 #include "vq_wide.inc"
+#include "vq_assign.inc"
 
 typedef void (*vq_search_reg_fn)(const float*, const float*, const float*, float*, float*, int64_t*, int, int, int, int,
                                  int);
@@ -637,6 +639,12 @@ int msmc_vq_search_stream(const float* x, const float* embed_t, const float* eno
 int msmc_vq_search_wide(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff, int64_t* ind,
                         int N, int d, int K, msmc_stream stream) {
     return vq_wide_launch(x, embed_t, enorm, quant, diff, ind, N, d, K, stream);
+}
+
+// ... its labels and the squared distance to the winner alone (vq_assign.inc)
+int msmc_vq_assign_wide(const float* x, const float* embed_t, const float* enorm, int64_t* ind, float* dist, int N, int d, int K,
+                        msmc_stream stream) {
+    return vq_assign_launch(x, embed_t, enorm, ind, dist, N, d, K, stream);
 }
 
 // ---- shortlist search (vq_shortlist.inc) ----------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 // their rows hold.  After the last tile the four lane groups of a frame, then the WC waves (through LDS), are merged with the
 // index as tie-break: the first minimum.  The winner's row then comes from embed_t in global memory (L2) and quant / diff are
 // formed by the resident kernels' epilogue expression; the WC waves of a frame split the row's 16-byte pieces.
+// Everything up to the merged (best, index) is vq_wide_argmin, which the labels-only kernel of vq_assign.inc calls as well.
 // No atomics; every global store is a vector-memory store.  quant may alias x: a workgroup reads only its own frames' rows,
 // and the last of those reads is behind a workgroup barrier before the first store.
 
@@ -20,12 +21,12 @@
 static int vq_wide_split = 0;
 extern "C" void msmc_vq_wide_set_split(int wc) { vq_wide_split = wc; }
 
+// The search itself, shared by vq_search_wide_kernel and vq_assign_wide_kernel (vq_assign.inc): the whole workgroup calls it
+// and every lane (f, g) of the WC waves of a frame tile returns with the frame's first minimum (best, bi).  smem: the
+// workgroup's dynamic LDS, of which it uses the first vqw_lds_bytes(WC) bytes; the callers' epilogues differ, the labels cannot.
 template <int WC>
-__global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* x, const float* __restrict__ embed_t,
-                                                            const float* __restrict__ enorm, float* quant,
-                                                            float* __restrict__ diff, int64_t* __restrict__ ind, int N, int d,
-                                                            int K) {
-    MSMC_DYN_LDS(smem);
+MSMC_DEV_INLINE void vq_wide_argmin(char* smem, const float* x, const float* __restrict__ embed_t,
+                                    const float* __restrict__ enorm, int N, int d, int K, float& best, int& bi) {
     constexpr int WF = 4 / WC, FT = 16 * WF, KT = WIDE_KT * WC, ROWS = FT + KT;
     float* sl = (float*)smem;                                   // [2][ROWS][WIDE_PITCH]: frame rows, then centroid rows
     float* en = sl + 2 * ROWS * WIDE_PITCH;                     // [2][KT]
@@ -47,8 +48,9 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* x, con
     __syncthreads();
 
     int buf = 0;
-    float xx = 0.f, best = inf;
-    int bi = 0;
+    float xx = 0.f;
+    best = inf;
+    bi = 0;
     f32x4 acc[4];
     for (int q = 0; q < total; ++q) {
         const int kt = q / nds, s = q - kt * nds;
@@ -104,6 +106,22 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* x, con
             if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
         }
     }
+}
+
+template <int WC>
+__global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* x, const float* __restrict__ embed_t,
+                                                            const float* __restrict__ enorm, float* quant,
+                                                            float* __restrict__ diff, int64_t* __restrict__ ind, int N, int d,
+                                                            int K) {
+    MSMC_DYN_LDS(smem);
+    constexpr int WF = 4 / WC, FT = 16 * WF;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int f = lane & 15, g = lane >> 4;
+    const int wf = w / WC, wc = w - wf * WC;
+    const int n0 = blockIdx.x * FT;
+    float best;
+    int bi;
+    vq_wide_argmin<WC>(smem, x, embed_t, enorm, N, d, K, best, bi);
 
     const int n = n0 + wf * 16 + f;
     if (n < N) {
@@ -126,9 +144,16 @@ __global__ __launch_bounds__(256) void vq_search_wide_kernel(const float* x, con
 
 typedef void (*vq_search_wide_fn)(const float*, const float*, const float*, float*, float*, int64_t*, int, int, int);
 
-static inline size_t vqw_lds_bytes(int wc) {
-    const int ft = 64 / wc, kt = WIDE_KT * wc;
-    return (wide_lds_floats(ft, kt) + 2 * wc * ft) * sizeof(float);
+static constexpr size_t vqw_lds_bytes(int wc) {
+    return (wide_lds_floats(64 / wc, WIDE_KT * wc) + 2 * wc * (64 / wc)) * sizeof(float);
+}
+
+// waves per frame tile for N frames: the tests' switch, else the choice argued in vq_wide_launch (one place: the assignment of
+// vq_assign.inc must run the instantiation the search would)
+static inline int vq_wide_pick_split(int N) {
+    const int wc = vq_wide_split;
+    if (wc == 1 || wc == 2 || wc == 4) return wc;
+    return N <= 32 * MSMC_NUM_CU ? 4 : ((N + 63) / 64 >= MSMC_NUM_CU ? 1 : 2);
 }
 
 static int vq_wide_launch(const float* x, const float* embed_t, const float* enorm, float* quant, float* diff, int64_t* ind,
@@ -141,8 +166,7 @@ static int vq_wide_launch(const float* x, const float* embed_t, const float* eno
     // on an MI355X (profiles/kmeans_vq.md; d = 1024, K = 1000): N = 6400: 867 / 450 / 318 us for WC = 1 / 2 / 4;
     // N = 2^17: 3.53 / 3.72 / 5.04 ms.  WC = 4 while all its workgroups are resident at once (two per CU: N <= 8192),
     // WC = 1 once the 64-frame workgroups fill every CU, WC = 2 in between (that range is not measured).
-    int wc = vq_wide_split;
-    if (wc != 1 && wc != 2 && wc != 4) wc = N <= 32 * MSMC_NUM_CU ? 4 : ((N + 63) / 64 >= MSMC_NUM_CU ? 1 : 2);
+    const int wc = vq_wide_pick_split(N);
     vq_search_wide_fn fn = wc == 1 ? vq_search_wide_kernel<1> : wc == 2 ? vq_search_wide_kernel<2> : vq_search_wide_kernel<4>;
     const size_t lds = vqw_lds_bytes(wc);
     int rc = msmc_allow_lds((const void*)fn, (int)lds);

@@ -21,7 +21,7 @@
 // the shapes the wide kernels take: whole 16-channel groups, any number of centroids
 static inline bool wide_takes(int d, int K) { return d >= 16 && d <= WIDE_MAX_D && d % 16 == 0 && K >= 1; }
 // floats of LDS of the two slice buffers and the two norm tiles
-static inline size_t wide_lds_floats(int ft, int kt) { return (size_t)2 * (ft + kt) * WIDE_PITCH + 2 * kt; }
+static constexpr size_t wide_lds_floats(int ft, int kt) { return (size_t)2 * (ft + kt) * WIDE_PITCH + 2 * kt; }
 
 // 16-channel groups of the slice that starts at channel s0: 2, or 1 for the last slice of d % 32 == 16
 MSMC_DEV int wide_groups(int d, int s0) { return d - s0 < WIDE_DS ? 1 : 2; }

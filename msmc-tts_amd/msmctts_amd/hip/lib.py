@@ -32,6 +32,7 @@ _SIGNATURES = {
     'msmc_vq_search': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'msmc_vq_search_stream': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'msmc_vq_search_wide': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'msmc_vq_assign_wide': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_vq_shortlist_bytes': (_sz, [_i, _i, _i]),
     'msmc_vq_prepare_shortlist': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_vq_search_shortlist': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -45,6 +46,8 @@ _SIGNATURES = {
     'msmc_kmeans_update': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     'msmc_kmeanspp_workspace': (_sz, [_i, _i, _i, _i]),
     'msmc_kmeanspp_seed': (_i, [_vp, _i, _i, _i, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'msmc_units_collapse': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    'msmc_units_usage': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -24,7 +24,9 @@ the optional global encoder and frame decoder and the vocoder.  Same class names
 ``window`` / ``window_frames`` forms of ``MSMCVQGANEmb.forward``.  ``quantizer_path`` is a pickle holding an object with
 ``cluster_centers_`` [K, d] as in the reference (unpickling a scikit-learn model needs scikit-learn installed; nothing here
 imports it) or, in addition, a ``.npy`` file of shape [K, d] -- which ``fit_kmeans`` (hip/kmeans.py, exported here: Lloyd's
-algorithm on the gfx950 kernels) produces from frames [N, d].  Deviations from the reference:
+algorithm on the gfx950 kernels) produces from frames [N, d].  The step between fitting and training -- frames to units -- is
+``assign_units`` / ``collapse_units`` / ``unit_usage`` / ``usage_summary`` (hip/units.py, exported here too) and
+``KMeansQuantizer.units``: labels only, through ``msmc_vq_assign_wide``.  Deviations from the reference:
 
 * the reference assigns ``embed`` from the file at every forward (:316), so a checkpoint's ``embed`` never counts.  Here the
   centroids are copied into the buffer at construction and again after every ``load_state_dict``: the same observable result;
@@ -45,6 +47,9 @@ import torch.nn.functional as F
 from ...hip import norm as hipnorm
 from ...hip import window as hipwindow
 from ...hip.kmeans import fit_kmeans, kmeans_plusplus  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
+from ...hip import units as hipunits
+from ...hip import vq as hipvq
+from ...hip.units import assign_units, collapse_units, unit_usage, usage_summary  # noqa: F401  -- frames -> units on that file
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
 from .modules import Quantize
@@ -241,6 +246,20 @@ class KMeansQuantizer(nn.Module):
         outputs, diffs, indices = zip(*states)
         return {'residual_output': None, 'quantizer_outputs': outputs, 'quantizer_diffs': diffs, 'quantizer_indices': indices,
                 'quantizer_lengths': [length for _, length in encoder_states], 'predictor_diffs': None}
+
+    def units(self, emb, emb_length, collapse=False):
+        """emb [B, T, d] -> labels [B, T] int64 without quant and diff (``msmc_vq_assign_wide`` on this module's centroids, no
+        gradient): the ``quantizer_indices`` of ``forward`` wherever that runs the wide search -- every single head
+        ``msmc_vq_search`` refuses, unit codebooks among them -- since the two kernels share the search.  ``collapse``: also the
+        runs of the valid prefixes, ``(labels, units [B, T], dur [B, T] int32, ulen [B])`` (``collapse_units``)."""
+        B, T, d = emb.shape
+        with torch.no_grad():
+            embed_t, enorm = hipvq.vq_prepare(self.quantizer[0].embed.unsqueeze(0), frames=0)
+            labels, _ = hipunits.assign_wide(emb.detach().reshape(B * T, d).float(), embed_t, enorm, want_dist=False)
+            labels = labels.view(B, T)
+            if not collapse:
+                return labels
+            return (labels,) + hipunits.collapse_units(labels, emb_length)
 
 
 class KMeansVQGANEmb(nn.Module):
