@@ -135,6 +135,34 @@ int msmc_vq_ema_stats(const float* x, const int64_t* ind, const int64_t* length,
 int msmc_vq_ema_apply(float* stats, float* embed, float* cluster_size, float* embed_avg, int D, int H, int K,
                       float decay, float eps, msmc_stream stream);
 
+/* The same update for ONE wide head, beyond d = 512 (msmc-tts_amd/csrc/ema_wide.hip): the shapes of msmc_vq_search_wide,
+ * d % 16 == 0, 16 <= d <= 2048, K >= 1, with N = B*T >= 1, N * d * 4 < 2^32 and x / stats / workspace 16-byte aligned;
+ * anything else returns MSMC_E_SHAPE with nothing launched and nothing written.  x [B*T][d], ind [B*T], length [B] int64,
+ * embed / embed_avg [d][K], cluster_size [K].  Frames with t >= length[b] are never read.
+ * _workspace: bytes of scratch of _update: 8 N rounded up to 16 for the masked labels, msmc_kmeans_stats_workspace(N, d, K), and
+ * 4 K (d + 2) for a stats block; 0 for a refused shape.  _stats needs the first two parts only.  A shorter workspace:
+ * MSMC_E_WORKSPACE.
+ * _stats: lab[n] = ind[n] where t < length[b] (n = b*T + t), else -1, then the launches of msmc_kmeans_stats on (x, lab): stats =
+ * [K][d] sums, [K] counts, K floats of scratch for _apply -- the layout of msmc_vq_ema_stats with H = 1.  _apply: the buffer
+ * update from stats (summed over ranks where the host does that).  _update: _stats into the workspace's stats block, then
+ * _apply; bit-identical to calling the two.
+ * Fixed order of every operation (same inputs, same bits; no floating-point atomics): the sums in the run order of
+ * msmc_kmeans_stats (below); omd = (float)(1.0 - (double)decay), keps = (float)((double)K * (double)eps);
+ * cs_new[k] = fmaf(counts[k], omd, cluster_size[k] * decay); n = the sum of cs_new as msmc_vq_ema_update forms it: 256 partials
+ * p[t] = ((+0 + cs_new[t]) + cs_new[t + 256]) + ..., then p[t] = p[t] + p[t + s] for t < s, s = 128, 64, .. 1, n = p[0];
+ * sm[k] = (cs_new[k] + eps) / (n + keps) * n, left to right; embed_avg[j][k] = fmaf(sums[k][j], omd, embed_avg[j][k] * decay);
+ * embed[j][k] = embed_avg[j][k] / sm[k]; cluster_size[k] = cs_new[k].  Every operation named is one IEEE fp32 operation.
+ * On a shape msmc_vq_ema_update takes as well, counts and cluster_size are bit-identical to it; embed and embed_avg differ by the
+ * summation order of the sums alone. */
+size_t msmc_vq_ema_wide_workspace(int N, int d, int K);
+int msmc_vq_ema_wide_stats(const float* x, const int64_t* ind, const int64_t* length, float* stats, void* workspace,
+                           size_t workspace_bytes, int B, int T, int d, int K, msmc_stream stream);
+int msmc_vq_ema_wide_apply(float* stats, float* embed, float* cluster_size, float* embed_avg, int d, int K, float decay,
+                           float eps, msmc_stream stream);
+int msmc_vq_ema_wide_update(const float* x, const int64_t* ind, const int64_t* length, float* embed, float* cluster_size,
+                            float* embed_avg, void* workspace, size_t workspace_bytes, int B, int T, int d, int K, float decay,
+                            float eps, msmc_stream stream);
+
 /* Backward of (quant, diff) wrt x:  gx = g_quant + g_diff * 2*(x - quant)/H   (straight-through +
  * the un-reduced commitment term, modules.py:59-60).  g_diff may be NULL (treated as zero). */
 int msmc_vq_backward(const float* g_quant, const float* g_diff, const float* x, const float* quant,

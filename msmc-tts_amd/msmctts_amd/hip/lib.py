@@ -40,6 +40,10 @@ _SIGNATURES = {
     'msmc_vq_ema_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _f, _f, _vp]),
     'msmc_vq_ema_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     'msmc_vq_ema_apply': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp]),
+    'msmc_vq_ema_wide_workspace': (_sz, [_i, _i, _i]),
+    'msmc_vq_ema_wide_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    'msmc_vq_ema_wide_apply': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp]),
+    'msmc_vq_ema_wide_update': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _f, _vp]),
     'msmc_vq_backward': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'msmc_kmeans_stats_workspace': (_sz, [_i, _i, _i]),
     'msmc_kmeans_stats': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),

@@ -62,6 +62,11 @@ def wide_takes(H, d, K):
     return H == 1 and d % 16 == 0 and 16 <= d <= 2048 and K >= 1
 
 
+def ema_resident_takes(H, d, K):
+    """the shapes ``msmc_vq_ema_update`` (csrc/vq.hip: a tile's rows of one head staged in LDS) takes"""
+    return H >= 1 and K >= 1 and d % 4 == 0 and d <= 512
+
+
 def _search_wide(xc, embed_t, enorm, quant, diff, ind, N, d, K):
     lib.call('msmc_vq_search_wide', lib.ptr(xc), lib.ptr(embed_t, torch.float32), lib.ptr(enorm, torch.float32), lib.ptr(quant),
              lib.ptr(diff), lib.ptr(ind), N, d, K, lib.stream(xc))
@@ -173,25 +178,41 @@ def join_ema(device):
         _EMA['used'] = None
 
 
-def vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace=None):
+def vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace=None, wide=False):
     """In-place EMA update of the packed buffers embed [H,d,K], cluster_size [H,K], embed_avg [H,d,K]
-    from the valid frames of x [B,T,D] / ind [B,T,H] (t < length[b])."""
+    from the valid frames of x [B,T,D] / ind [B,T,H] (t < length[b]).  ``wide=True``: ``msmc_vq_ema_wide_update``
+    (csrc/ema_wide.hip) whatever the shape -- one head of a width the wide search takes (``wide_takes``), d up to 2048; its sums
+    follow the run order of ``msmc_kmeans_stats``, so ``embed`` / ``embed_avg`` differ from the resident kernels' in the last bits
+    where both take the shape.  The default reaches ``msmc_vq_ema_update`` for every shape (d <= 512)."""
     side = _EMA['side'] if x.is_cuda else None
     if side is not None:
         side.wait_stream(torch.cuda.current_stream(x.device))
         _EMA['used'] = side
         with torch.cuda.stream(side):
-            return _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace)
-    return _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace)
+            return _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace, wide)
+    return _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace, wide)
 
 
-def _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace=None):
+def _one_wide_head(H, name):
+    if H != 1:
+        raise RuntimeError('%s takes one head (got %d)' % (name, H))
+
+
+def _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, workspace=None, wide=False):
     B, T, D = x.shape
     H, d, K = embed.shape
-    workspace = lib.workspace(int(lib.get().msmc_vq_ema_workspace(B * T, D, H, K)), x.device, workspace)
+    if wide:
+        _one_wide_head(H, 'msmc_vq_ema_wide_update')
+    nbytes = lib.get().msmc_vq_ema_wide_workspace(B * T, d, K) if wide else lib.get().msmc_vq_ema_workspace(B * T, D, H, K)
+    workspace = lib.workspace(int(nbytes), x.device, workspace)
     xc = _f32_frames(x.detach())
     indc = ind.contiguous()                 # (named: a temporary would be released before the launch reads it)
     length = length.to(device=x.device, dtype=torch.int64).contiguous()
+    if wide:
+        lib.call('msmc_vq_ema_wide_update', lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(embed, torch.float32),
+                 lib.ptr(cluster_size, torch.float32), lib.ptr(embed_avg, torch.float32), lib.ptr(workspace),
+                 workspace.numel() * workspace.element_size(), B, T, d, K, float(decay), float(eps), lib.stream(xc))
+        return workspace
     lib.call('msmc_vq_ema_update', lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(embed, torch.float32),
              lib.ptr(cluster_size, torch.float32), lib.ptr(embed_avg, torch.float32), lib.ptr(workspace),
              workspace.numel() * workspace.element_size(), B, T, D, H, K, float(decay), float(eps), lib.stream(xc))
@@ -201,10 +222,14 @@ def _vq_ema_update(x, ind, length, embed, cluster_size, embed_avg, decay, eps, w
 # -- data-parallel codebook synchronisation (opt-in; the reference's ranks EMA-update from their local batch) ----------
 class CodebookSync(object):
     """Pending EMA statistics of one quantiser stage: this rank's [H][K][d] sums + [H][K] counts in a persistent buffer
-    (static across hipGraph replays), applied to the packed buffers after the cross-rank sum."""
+    (static across hipGraph replays), applied to the packed buffers after the cross-rank sum.  ``wide``: the two halves of
+    ``msmc_vq_ema_wide_update`` (one wide head; the same layout of the statistics)."""
 
-    def __init__(self, embed, cluster_size, embed_avg, decay, eps):
+    def __init__(self, embed, cluster_size, embed_avg, decay, eps, wide=False):
         H, d, K = embed.shape
+        if wide:
+            _one_wide_head(H, 'msmc_vq_ema_wide_stats')
+        self.wide = bool(wide)
         self.embed, self.cluster_size, self.embed_avg, self.decay, self.eps = embed, cluster_size, embed_avg, decay, eps
         self.stats = torch.zeros(H * K * (d + 2), dtype=torch.float32, device=embed.device)   # sums, counts, scratch
         self.workspace = None
@@ -215,15 +240,25 @@ class CodebookSync(object):
     def collect(self, x, ind, length):
         B, T, D = x.shape
         H, d, K = self.embed.shape
-        self.workspace = lib.workspace(int(lib.get().msmc_vq_ema_workspace(B * T, D, H, K)), x.device, self.workspace)
+        nbytes = lib.get().msmc_vq_ema_wide_workspace(B * T, d, K) if self.wide else lib.get().msmc_vq_ema_workspace(B * T, D, H, K)
+        self.workspace = lib.workspace(int(nbytes), x.device, self.workspace)
         xc = x.detach().contiguous().float()
         indc = ind.contiguous()
         length = length.to(device=x.device, dtype=torch.int64).contiguous()
+        if self.wide:
+            lib.call('msmc_vq_ema_wide_stats', lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(self.stats),
+                     lib.ptr(self.workspace), self.workspace.numel() * 4, B, T, d, K, lib.stream(xc))
+            return
         lib.call('msmc_vq_ema_stats', lib.ptr(xc), lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(self.stats),
                  lib.ptr(self.workspace), self.workspace.numel() * 4, B, T, D, H, K, lib.stream(xc))
 
     def apply(self):
         H, d, K = self.embed.shape
+        if self.wide:
+            lib.call('msmc_vq_ema_wide_apply', lib.ptr(self.stats), lib.ptr(self.embed, torch.float32),
+                     lib.ptr(self.cluster_size, torch.float32), lib.ptr(self.embed_avg, torch.float32), d, K,
+                     float(self.decay), float(self.eps), lib.stream(self.stats))
+            return
         lib.call('msmc_vq_ema_apply', lib.ptr(self.stats), lib.ptr(self.embed, torch.float32),
                  lib.ptr(self.cluster_size, torch.float32), lib.ptr(self.embed_avg, torch.float32), H * d, H, K,
                  float(self.decay), float(self.eps), lib.stream(self.stats))

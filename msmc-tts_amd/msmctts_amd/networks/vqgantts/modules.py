@@ -10,8 +10,10 @@ tensors so the kernels see [H][d][K] while ``state_dict`` keeps the reference ke
 
 A single-head ``Quantize`` whose shape ``msmc_vq_search`` refuses (``n_embed % 16 != 0``, or an ``embed_dim`` beyond what the
 streamed launcher fits: the k-means unit codebooks, d = 1024) searches on ``msmc_vq_search_wide`` (csrc/vq_wide.inc; hip/vq.py
-routes it) where that kernel takes the shape; the backward is ``msmc_vq_backward`` either way.  The EMA kernels keep their
-``d <= 512`` limit: ``forward(update=True)`` in training beyond it raises.
+routes it) where that kernel takes the shape; the backward is ``msmc_vq_backward`` either way.  The resident EMA kernels keep
+their ``d <= 512`` limit: ``forward(update=True)`` in training beyond it raises unless ``ema_wide`` is set on the module
+(``VQGANTrainer(wide_codebook_update=True)`` sets it), which sends such a head to ``msmc_vq_ema_wide_update``
+(csrc/ema_wide.hip: one head, d % 16 == 0 up to 2048).
 """
 import torch
 import torch.nn as nn
@@ -37,13 +39,16 @@ def _ranking(input, embed):
 def _ema(q, x3, ind, length, embed, cs, ea):
     """EMA codebook update of one stage: fused (reference semantics: this rank's frames only) or, with
     ``q.sync_stats`` (VQGANTrainer sync_codebook_stats=True), statistics now and the update after the cross-rank sum
-    (hip/vq.py flush_codebook_sync, called by the trainer between forward and backward)."""
+    (hip/vq.py flush_codebook_sync, called by the trainer between forward and backward).  With ``q.ema_wide`` a shape
+    ``msmc_vq_ema_update`` refuses (d > 512) runs the wide kernels (csrc/ema_wide.hip); every shape it takes keeps its kernel
+    and its bits."""
+    wide = bool(getattr(q, 'ema_wide', False)) and not hipvq.ema_resident_takes(*embed.shape)
     if not getattr(q, 'sync_stats', False):
-        q._ws = hipvq.vq_ema_update(x3, ind, length, embed, cs, ea, q.decay, q.eps, q._ws)
+        q._ws = hipvq.vq_ema_update(x3, ind, length, embed, cs, ea, q.decay, q.eps, q._ws, wide=wide)
         return
     cb = getattr(q, '_sync', None)
-    if cb is None or not cb.matches(embed):
-        cb = q._sync = hipvq.CodebookSync(embed, cs, ea, q.decay, q.eps)
+    if cb is None or not cb.matches(embed) or cb.wide != wide:
+        cb = q._sync = hipvq.CodebookSync(embed, cs, ea, q.decay, q.eps, wide=wide)
     cb.collect(x3, ind, length)
     if not any(c is cb for c in hipvq.PENDING):
         hipvq.PENDING.append(cb)
@@ -51,6 +56,8 @@ def _ema(q, x3, ind, length, embed, cs, ea):
 
 class Quantize(nn.Module):
     """Single-codebook EMA quantiser (reference modules.py:10-116)."""
+
+    ema_wide = False            # opt-in: the wide EMA update where the resident kernels refuse the width (see _ema)
 
     def __init__(self, embed_dim, n_embed, decay=0.99, eps=1e-5):
         super().__init__()

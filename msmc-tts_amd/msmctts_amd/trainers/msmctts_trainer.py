@@ -23,6 +23,7 @@ import torch.nn.functional as F
 from ..hip import convnet as hipconvnet
 from ..hip import losses as hiploss
 from ..hip import vq as hipvq
+from ..networks.vqgantts.modules import Quantize
 from ..utils.utils import get_mask_from_lengths
 from .base_trainer import BaseTrainer
 from .criterions.stft_loss import MelLoss, MultiResolutionSTFTLoss
@@ -98,7 +99,7 @@ class VQGANTrainer(BaseTrainer):
     def __init__(self, config, model, num_gpus=1, rank=0, warmup_steps=0, lambda_frame=1.0,
                  eval_inteval_iters=1000, grad_clip_thresh=1.0, sample_lengths=24000, lambda_vq=1, lambda_pr=1,
                  lambda_fm=2, lambda_stft=45, stft_loss_func='mel_loss', stft_loss_config=None,
-                 sync_codebook_stats=False):
+                 sync_codebook_stats=False, wide_codebook_update=False):
         super().__init__(config, model, num_gpus, rank)
         # Not in the reference (its ranks EMA-update their VQ codebooks from the local batch and rank 0's copy is the
         # one checkpointed): sum the EMA statistics over ranks -- one small all-reduce per step -- so that every rank
@@ -107,6 +108,12 @@ class VQGANTrainer(BaseTrainer):
         for m in self.model.modules():
             if hasattr(m, 'decay') and hasattr(m, 'n_embed'):
                 m.sync_stats = self.sync_codebook_stats
+        # A single-head codebook wider than the resident EMA kernels take (d > 512; the reference has no such limit) updates
+        # on the wide kernels (csrc/ema_wide.hip) when this is set; without it such a stage raises at its first update.
+        self.wide_codebook_update = bool(wide_codebook_update)
+        for m in self.model.modules():
+            if isinstance(m, Quantize):
+                m.ema_wide = self.wide_codebook_update
         self.lambda_frame, self.warmup_steps = lambda_frame, warmup_steps
         self.frameshift = self.config.dataset.frameshift[self.config.dataset.feature.index('mel')]
         self.frame_lengths = -1 if sample_lengths == -1 else sample_lengths // self.frameshift
