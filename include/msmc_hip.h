@@ -244,6 +244,52 @@ int msmc_units_collapse(const int64_t* ind, const int64_t* length, int64_t* unit
 int msmc_units_usage(const int64_t* ind, const int64_t* length, int64_t* counts, int B, int T, int K, int accumulate,
                      msmc_stream stream);
 
+/* total[b] = the int64 sum of max(dur[b][r], 0) over r < min(max(ulen[b], 0), R): the frames msmc_units_expand makes of
+ * utterance b when T does not cut them.  dur [B][R] int32, ulen [B] int64, total [B] int64.  Nothing at or beyond ulen[b] is
+ * read.  B <= 0 or R <= 0: MSMC_E_SHAPE. */
+int msmc_units_total(const int32_t* dur, const int64_t* ulen, int64_t* total, int B, int R, msmc_stream stream);
+
+/* The inverse of msmc_units_collapse: units [B][R] int64, dur [B][R] int32, ulen [B] int64 -> ind [B][T] int64, length [B]
+ * int64.  Run r < min(max(ulen[b], 0), R) of utterance b covers the frames [s_r, s_r + max(dur[b][r], 0)), s_r = the sum of
+ * max(dur, 0) over the runs before it, in 64 bits; total = that sum over all runs.  ind[b][t] = units[b][r] of the run that
+ * covers t for t < min(total, T), -1 from there on; length[b] = min(total, T).  Runs of zero or negative duration make no
+ * frame.  Every element of ind and length is written exactly once; nothing at or beyond ulen[b] is read.  One workgroup per
+ * utterance, 256 runs at a time, any R and T; consecutive work-items write consecutive frames.
+ * B <= 0, R <= 0 or T <= 0: MSMC_E_SHAPE, nothing launched. */
+int msmc_units_expand(const int64_t* units, const int32_t* dur, const int64_t* ulen, int64_t* ind, int64_t* length, int B, int R,
+                      int T, msmc_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * UE  the decoder input of KMeansVQGANEmb from unit labels (msmc-tts_amd/csrc/unit_embed.hip; host side msmctts_amd/hip/units.py
+ * unit_embed).  The reference embeds the labels, runs the nearest-centroid search on the result and then in_linear
+ * (msmc_vqgan_emb.py:440-446); with a frozen codebook that is a row of table = centers W^T + b [K][C].
+ * A row (b, t) is VALID when t < length[b] and 0 <= ind[b][t] < K.  ind [B][T] int64, length [B] int64, fp32 elsewhere.
+ * Shapes: C % 8 == 0, 8 <= C <= 2048, K >= 1, B >= 1, T >= 1, every fp32 pointer (and the workspace) 16-byte aligned; the
+ * backward also needs B T C 4 < 2^32.  Anything else: MSMC_E_SHAPE, nothing launched, nothing written.
+ * ------------------------------------------------------------------------------------------- */
+
+/* out[b][t][:] = table[ind[b][t]][:] + glob[b][:] on the valid rows -- one fp32 add per element, none when glob is NULL (then
+ * the row is the table's, bit for bit) -- and +0 in every other row.  table [K][C], glob [B][C] or NULL, out [B][T][C].  The
+ * table is never read at an invalid label; every element of out is written exactly once (16-byte loads and stores). */
+int msmc_units_embed_fwd(const int64_t* ind, const int64_t* length, const float* table, const float* glob, float* out, int B, int T,
+                         int C, int K, msmc_stream stream);
+
+/* Bytes of scratch that are enough for msmc_units_embed_bwd on N = B T frames whatever B is: two int64 label arrays 8 N (each
+ * rounded up to 16), 4 max(K, N) of counts (rounded up to 16) and the larger of msmc_kmeans_stats_workspace(N, C, K) and
+ * (N, C, N).  0 for a refused shape.  (A call needs the same with its own B in the place of N, which is never more.) */
+size_t msmc_units_embed_workspace(int N, int C, int K);
+
+/* The gradient of msmc_units_embed_fwd: gtable[k] = the sum of gout[n] over the valid rows labelled k, gglob[b] = the sum of
+ * gout[b][t] over the valid rows of utterance b (skipped when gglob is NULL).  gout [B][T][C], gtable [K][C], gglob [B][C]:
+ * both are overwritten, not accumulated; rows without a valid frame come out +0.
+ * Fixed order (same inputs, same bits; no floating-point atomics): lab[n] = ind[n] on the valid rows, -1 elsewhere, and the
+ * launches of msmc_kmeans_stats on (gout, lab) with K labels; ulab[n] = b on the valid rows, -1 elsewhere, and the same launches
+ * on (gout, ulab) with B labels.  So, per channel: the rows of a label (of an utterance) in ascending n (t) are cut into runs of
+ * 64; a run partial is (((+0 + g[n_0]) + g[n_1]) + ...), the total (((+0 + partial_0) + partial_1) + ...).
+ * MSMC_E_WORKSPACE for a workspace shorter than the call needs (see msmc_units_embed_workspace). */
+int msmc_units_embed_bwd(const float* gout, const int64_t* ind, const int64_t* length, float* gtable, float* gglob, void* workspace,
+                         size_t workspace_bytes, int B, int T, int C, int K, msmc_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * G1/G2/D1/D2 channels-last implicit-GEMM convolution family on the matrix cores.
  * Replaces the cuDNN/MIOpen convolutions behind

@@ -71,6 +71,8 @@ class DeviceLoader(object):
             out['mel_length_host'] = host_lengths
         if host_emb_lengths is not None:
             out['emb_length_host'] = host_emb_lengths
+        if 'units_length' in batch:                    # (a batch of stored unit labels: the same, for ``forward_units``)
+            out['units_length_host'] = batch['units_length'].tolist()
         return out
 
     def __iter__(self):

@@ -52,6 +52,11 @@ _SIGNATURES = {
     'msmc_kmeanspp_seed': (_i, [_vp, _i, _i, _i, _i, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'msmc_units_collapse': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     'msmc_units_usage': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'msmc_units_total': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    'msmc_units_expand': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    'msmc_units_embed_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'msmc_units_embed_workspace': (_sz, [_i, _i, _i]),
+    'msmc_units_embed_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
 }
 
 

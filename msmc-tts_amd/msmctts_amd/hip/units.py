@@ -7,6 +7,10 @@ wide=True)`` stores 2 d 4 of quant and diff.  ``collapse_units`` cuts label sequ
 ``unit_usage`` counts the frames per code (csrc/units.hip); ``usage_summary`` turns the counts into the two numbers the
 reference prints (examples/qs-tts/scripts/vq_analysis.py ``compute_codebook_complexity``): codes used and their entropy in bits.
 
+The way back: ``expand_units`` turns (unit, duration) runs into frame labels again (csrc/units.hip) and ``unit_embed`` turns
+frame labels into the synthesiser's decoder input -- rows of the projected codebook plus the utterance's global embedding, with
+its gradient (csrc/unit_embed.hip): what ``KMeansVQGANEmb.forward_units`` / ``synthesis_units`` run.
+
 There is no CPU path and no fallback: shapes the kernels refuse raise with the launcher's code, host frames are uploaded block
 by block, and without the library (or with a host ``device`` on the product build) the calls raise.
 """
@@ -122,6 +126,75 @@ def unit_usage(ind, length, K, counts=None):
     lib.call('msmc_units_usage', lib.ptr(indc, torch.int64), lib.ptr(length), lib.ptr(counts, torch.int64), B, T, K,
              int(accumulate), lib.stream(indc))
     return counts
+
+
+def expand_units(units, dur, ulen, T=None):
+    """The inverse of ``collapse_units``: units [B, R] int64, dur [B, R] (int32), ulen [B] -> ``(ind [B, T] int64, length [B]
+    int64)``.  Run r < ulen[b] covers ``max(dur[b, r], 0)`` frames; ``ind[b, t]`` is the unit of the run that covers frame t,
+    -1 behind the last run; ``length[b]`` the frames of utterance b, at most T (a longer sequence is cut).  ``T=None`` sizes the
+    output by the longest utterance (at least one frame): ``msmc_units_total`` and ONE read-back of its maximum, a
+    synchronisation -- pass T where it is known."""
+    if units.dim() != 2:
+        raise ValueError('units: expected [B, R], got %s' % (tuple(units.shape),))
+    unitsc = units.detach().contiguous()
+    B, R = unitsc.shape
+    durc = torch.as_tensor(dur).detach().to(device=unitsc.device, dtype=torch.int32).contiguous()
+    if tuple(durc.shape) != (B, R):
+        raise ValueError('dur: expected %s, got %s' % ((B, R), tuple(durc.shape)))
+    ulen = torch.as_tensor(ulen).to(device=unitsc.device, dtype=torch.int64).reshape(-1).contiguous()
+    if ulen.numel() != B:
+        raise ValueError('%d run counts for %d utterances' % (ulen.numel(), B))
+    if T is None:
+        total = torch.empty((max(B, 0),), dtype=torch.int64, device=unitsc.device)
+        lib.call('msmc_units_total', lib.ptr(durc), lib.ptr(ulen), lib.ptr(total), B, R, lib.stream(unitsc))
+        T = max(int(total.max()), 1)
+    T = int(T)
+    ind = torch.empty((B, max(T, 0)), dtype=torch.int64, device=unitsc.device)
+    length = torch.empty((B,), dtype=torch.int64, device=unitsc.device)
+    lib.call('msmc_units_expand', lib.ptr(unitsc, torch.int64), lib.ptr(durc), lib.ptr(ulen), lib.ptr(ind), lib.ptr(length), B, R, T,
+             lib.stream(unitsc))
+    return ind, length
+
+
+class _UnitEmbed(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ind, length, table, glob):
+        B, T = ind.shape
+        K, C = table.shape
+        tablec = table.detach().contiguous()
+        globc = None if glob is None else glob.detach().contiguous()
+        out = torch.empty((B, T, C), dtype=torch.float32, device=tablec.device)
+        lib.call('msmc_units_embed_fwd', lib.ptr(ind, torch.int64), lib.ptr(length, torch.int64), lib.ptr(tablec, torch.float32),
+                 lib.ptr(globc, torch.float32), lib.ptr(out), B, T, C, K, lib.stream(tablec))
+        ctx.save_for_backward(ind, length)
+        ctx.sizes = (B, T, C, K, glob is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        ind, length = ctx.saved_tensors
+        B, T, C, K, with_glob = ctx.sizes
+        goutc = gout.contiguous()
+        gtable = torch.empty((K, C), dtype=torch.float32, device=goutc.device)
+        gglob = torch.empty((B, C), dtype=torch.float32, device=goutc.device) if with_glob and ctx.needs_input_grad[3] else None
+        ws = lib.workspace(int(lib.get().msmc_units_embed_workspace(B * T, C, K)), goutc.device)
+        lib.call('msmc_units_embed_bwd', lib.ptr(goutc, torch.float32), lib.ptr(ind), lib.ptr(length), lib.ptr(gtable), lib.ptr(gglob),
+                 lib.ptr(ws), ws.numel() * ws.element_size(), B, T, C, K, lib.stream(goutc))
+        return None, None, gtable, gglob
+
+
+def unit_embed(ind, length, table, glob=None):
+    """The decoder input from unit labels: ind [B, T] int64, length [B], table [K, C] fp32, glob [B, C] fp32 or None ->
+    out [B, T, C] fp32 with ``out[b, t] = table[ind[b, t]] + glob[b]`` where ``t < length[b]`` and ``0 <= ind[b, t] < K``, zeros
+    in every other row (``msmc_units_embed_fwd``, csrc/unit_embed.hip).  Differentiable in ``table`` and ``glob``
+    (``msmc_units_embed_bwd``: per-label and per-utterance sums of the incoming gradient in the fixed order of the k-means
+    statistics pass, no atomics, same inputs same bits); ``ind`` and ``length`` get no gradient."""
+    indc, length = _labels_and_lengths(ind, length)
+    if table.dim() != 2:
+        raise ValueError('table: expected [K, C], got %s' % (tuple(table.shape),))
+    if glob is not None and tuple(glob.shape) != (indc.shape[0], table.shape[1]):
+        raise ValueError('glob: expected %s, got %s' % ((indc.shape[0], table.shape[1]), tuple(glob.shape)))
+    return _UnitEmbed.apply(indc, length, table, glob)
 
 
 def usage_summary(counts):

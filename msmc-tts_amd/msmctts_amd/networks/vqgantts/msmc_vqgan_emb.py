@@ -36,6 +36,14 @@ algorithm on the gfx950 kernels) produces from frames [N, d].  The step between 
   so its ``quantizer_lengths`` come out empty; nothing reads them there, and here they are the lengths given;
 * sizes the downstream kernels refuse (``n_model_size % 64``, ``mel_dim % 8`` with a global encoder) raise at construction, as
   for ``MSMCVQGANEmb``.
+
+The unit-input path (no reference counterpart): ``forward_units`` / ``synthesis_units`` take the stored labels [B, T] (or runs,
+through ``expand_units``) in the place of embedding frames.  With a frozen codebook ``in_linear(embed_code(ind))`` is a row of
+``unit_table() = centers W^T + b`` [K, n_model_size], so the decoder input is ``unit_embed`` (csrc/unit_embed.hip): one gather
+that also adds the global embedding, and for the gradient a per-label sum followed by the table's small GEMM -- no upload of
+frames, no nearest-centroid search, no ``in_linear`` over the frames.  Deviation from the frame path: padded rows (and rows whose
+label is outside [0, K)) of the decoder input are zeros there, where the frame path has whatever ``in_linear`` makes of the
+padding frames; the FFT blocks mask padded positions, so with a frame decoder the valid frames do not see the difference.
 """
 import pickle
 
@@ -50,6 +58,7 @@ from ...hip.kmeans import fit_kmeans, kmeans_plusplus  # noqa: F401  -- fits the
 from ...hip import units as hipunits
 from ...hip import vq as hipvq
 from ...hip.units import assign_units, collapse_units, unit_usage, usage_summary  # noqa: F401  -- frames -> units on that file
+from ...hip.units import expand_units, unit_embed  # noqa: F401  -- and units -> the decoder input (``forward_units``)
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
 from .modules import Quantize
@@ -130,6 +139,10 @@ class MSMCVQGANEmb(nn.Module):
     def _decode_frames(self, x, lengths, ref=None):
         if hasattr(self, 'global_encoder'):
             x = x + self.global_encoder(ref).unsqueeze(1).to(x.dtype)
+        return self._frame_decode(x, lengths)
+
+    def _frame_decode(self, x, lengths):
+        """the half of ``_decode_frames`` behind the global embedding (``KMeansVQGANEmb.forward_units`` adds that in its kernel)"""
         if hasattr(self, 'frame_decoder'):
             x, _ = self.frame_decoder(x, _fft_pos(lengths, x), lengths=lengths)
         return x
@@ -283,6 +296,7 @@ class KMeansVQGANEmb(nn.Module):
             self.mel_predictor = nn.Linear(n_model_size, mel_dim if mel_dim is not None else emb_dim)
 
     _decode_frames = MSMCVQGANEmb._decode_frames
+    _frame_decode = MSMCVQGANEmb._frame_decode
     _window = MSMCVQGANEmb._window
 
     def forward(self, emb, emb_length, pitch=None, energy=None, mel=None, ref=None, window='full', window_frames=None):
@@ -299,6 +313,55 @@ class KMeansVQGANEmb(nn.Module):
             dec_in = self._window(dec_in, window, window_frames)
             out['decoder_outputs'] = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
         return out
+
+    def unit_table(self):
+        """[K, n_model_size]: ``in_linear`` of every centroid, the rows ``forward_units`` gathers.  Differentiable in
+        ``in_linear``; computed anew at every call (the weights move with every optimizer step)"""
+        centers = self.quantizer.quantizer[0].embed.detach().t()
+        return F.linear(centers, self.in_linear.weight, self.in_linear.bias)
+
+    def _embed_units(self, ind, length, ref):
+        glob = None
+        if hasattr(self, 'global_encoder'):
+            glob = self.global_encoder(ref).float()
+        return unit_embed(ind, length, self.unit_table().float(), glob)
+
+    def forward_units(self, ind, length, mel=None, ref=None, window='full', window_frames=None):
+        """``forward`` from stored labels: ind [B, T] int64 (-1 or anything behind ``length``), length [B].  The dictionary of
+        ``forward`` with ``encoder_indices = (ind,)``; ``window`` / ``window_frames`` as there.  The decoder input is
+        ``unit_embed(ind, length, unit_table(), global embedding of ref or mel)``; the frame decoder, ``mel_predictor``, the
+        window and the vocoder follow as in ``forward``."""
+        if self.training:
+            hipnorm.advance_seed(ind.device)
+        out = {'encoder_indices': (ind,)}
+        dec_in = self._frame_decode(self._embed_units(ind, length, mel if ref is None else ref), length)
+        if hasattr(self, 'mel_predictor'):
+            out['mel_outputs'] = self.mel_predictor(dec_in)
+        if window is not None:
+            dec_in = self._window(dec_in, window, window_frames)
+            out['decoder_outputs'] = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
+        return out
+
+    def synthesis_units(self, ind, length=None, ref=None, dur=None, ulen=None):
+        """``synthesis`` from stored labels.  Without ``dur``: ind [B, T] frame labels, ``length`` [B] (None: every frame).
+        With ``dur`` [B, R]: ``ind`` holds the units of (unit, duration) runs, ``ulen`` [B] their number (None: every slot), and
+        the frame labels come from ``expand_units`` (one read-back to size them).  Returns what ``synthesis`` returns."""
+        if dur is not None:
+            if ulen is None:
+                ulen = torch.full((ind.shape[0],), ind.shape[1], dtype=torch.int64, device=ind.device)
+            ind, length = expand_units(ind, dur, ulen)
+        elif length is None:
+            length = torch.full((ind.shape[0],), ind.shape[1], dtype=torch.int64, device=ind.device)
+        if hasattr(self, 'global_encoder'):
+            assert ref is not None
+        dec_in = self._frame_decode(self._embed_units(ind, length, ref), length)
+        wav = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
+        if self.training:
+            out = {'decoder_outputs': wav}
+            if hasattr(self, 'mel_predictor'):
+                out['mel_outputs'] = self.mel_predictor(dec_in)
+            return out
+        return wav
 
     def analysis(self, emb, emb_length):
         if self.training:

@@ -45,6 +45,28 @@ def make_emb_batch(batch_size=16, frames=400, emb_dim=1024, mel_dim=80, hop=200,
     return batch
 
 
+def make_unit_batch(batch_size=16, frames=400, n_units=1000, mel_dim=80, hop=200, seed=1234, rank=0, device='cpu'):
+    """``make_emb_batch`` for stored unit labels (``EmbDataset.collate_fn`` on ``units`` files): ``units (B,T) int64`` uniform in
+    [0, n_units) with padding -1 and ``units_length`` in the place of ``emb`` / ``emb_length``; ``mel``, ``wav``, ``wav_length``
+    as there; ``units_length_host`` is the host list of the lengths."""
+    g = torch.Generator().manual_seed(seed + rank)
+    lengths = torch.randint(frames // 2, frames + 1, (batch_size,), generator=g)
+    lengths[0] = frames
+    lengths = torch.sort(lengths, descending=True).values.to(torch.int64)
+    units = torch.randint(0, n_units, (batch_size, frames), generator=g, dtype=torch.int64)
+    mel = torch.randn(batch_size, frames, mel_dim, generator=g)
+    wav = torch.rand(batch_size, frames * hop, 1, generator=g) * 2 - 1
+    valid = torch.arange(frames)[None, :] < lengths[:, None]
+    units = torch.where(valid, units, torch.full_like(units, -1))
+    mel = torch.where(valid[:, :, None], mel, torch.full_like(mel, -4.0))
+    s = torch.arange(frames * hop)[None, :, None]
+    wav = torch.where(s < (lengths * hop)[:, None, None], wav, torch.zeros_like(wav))
+    batch = {'units': units, 'units_length': lengths, 'mel': mel, 'wav': wav, 'wav_length': lengths * hop}
+    batch = {k: v.to(device) for k, v in batch.items()}
+    batch['units_length_host'] = lengths.tolist()
+    return batch
+
+
 def make_text_batch(mel_length, n_symbols=(100, 10, 2), phonemes=(30, 56), seed=4321, rank=0, device='cpu'):
     """The text side of a ``TTSDataset`` batch (reference msmctts/datasets/tts_dataset.py) for the given mel lengths:
     ``text (B, P, 3)`` symbol / tone / boundary ids (0 = padding), ``text_length (B,)``, ``dur (B, P)`` whole-frame durations of

@@ -21,6 +21,11 @@ which the reference's step fails with a ``KeyError``; here a model output withou
 loss dictionary carries no VQ keys (one guarded branch in ``VQGANTrainer._segment_a``).  Outputs that have ``encoder_diffs``
 behave as before.
 
+A batch of stored unit labels -- ``units`` int64 [B, T] with -1 padding and ``units_length`` in the place of ``emb`` /
+``emb_length`` (``EmbDataset`` on ``indices/`` files, ``synthetic.make_unit_batch``) -- goes to the model's ``forward_units``
+(``KMeansVQGANEmb``: no frames uploaded, no centroid search); a model without one raises ``TypeError``.  A batch with ``emb``
+behaves as before.
+
 ``stft_loss_supervised_step``: the reference reads ``self.stft_loss_supervised_step`` (:123) but no constructor sets it, and
 its own YAML passes it as a trainer kwarg (line 94) that its constructor would reject; here it is an ordinary kwarg.
 
@@ -77,11 +82,25 @@ class EmbVQGANTrainer(VQGANTrainer):
             seq = sorted(seq[:self.sample_batch_size])
         return [(i, self.rng.randrange(max(1, int(lengths[i]) - self.frame_lengths))) for i in seq]
 
+    @staticmethod
+    def _frames_key(batch):
+        """'emb', or 'units' for a batch of stored unit labels (``units`` int64 [B, T] with -1 padding, ``units_length``) that
+        carries no ``emb``: the feature whose ``<key>_length`` / ``<key>_length_host`` are the frame lengths and whose device is
+        the step's"""
+        return 'units' if 'emb' not in batch and 'units' in batch else 'emb'
+
     def _autoencode(self, st):
         b = st.batch
+        window_frames = None if st.frame_window is None else self.frame_lengths
+        if self._frames_key(b) == 'units':
+            model = self.model.autoencoder
+            if not hasattr(model, 'forward_units'):
+                raise TypeError('%s has no forward_units: a batch of unit labels (\'units\' without \'emb\') needs a model with a '
+                                'frozen codebook, such as KMeansVQGANEmb' % type(model).__name__)
+            return model.forward_units(b['units'], st.mel_length, mel=st.mel, window=st.frame_window, window_frames=window_frames)
         # (no ``ref``: a model with a global encoder embeds ``mel``)
         return self.model.autoencoder(b['emb'], st.mel_length, b.get('pitch'), b.get('energy'), mel=st.mel,
-                                      window=st.frame_window, window_frames=None if st.frame_window is None else self.frame_lengths)
+                                      window=st.frame_window, window_frames=window_frames)
 
     def _target(self, wav, pairs, win):
         """the waveform windows [n, frame_lengths * frameshift] fp32 at ``start * frameshift``"""
@@ -99,14 +118,15 @@ class EmbVQGANTrainer(VQGANTrainer):
         if reducer is not None:
             reducer.hooks_enabled = True
         st = _StepState()
-        st.phase, st.batch, st.mel, st.mel_length = phase, batch, batch['mel'], batch['emb_length']
+        key = self._frames_key(batch)
+        st.phase, st.batch, st.mel, st.mel_length = phase, batch, batch['mel'], batch[key + '_length']
         st.frame_window = st.target = None
         if phase > 0:
-            lengths = batch.get('emb_length_host')
+            lengths = batch.get(key + '_length_host')
             if lengths is None:
-                lengths = batch['emb_length'].tolist()
+                lengths = batch[key + '_length'].tolist()
             st.windows = pairs = self.sample_windows(lengths)
-            st.frame_window = hipwindow.as_windows(pairs, batch['emb'].device)
+            st.frame_window = hipwindow.as_windows(pairs, batch[key].device)
             st.target = self._target(batch['wav'].float(), pairs, st.frame_window)
         self._segment_a(st)
         self._sync_codebooks()
