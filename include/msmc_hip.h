@@ -291,6 +291,43 @@ int msmc_units_embed_bwd(const float* gout, const int64_t* ind, const int64_t* l
                          size_t workspace_bytes, int B, int T, int C, int K, msmc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * UC  the unit predictor's loss and label decoding (msmc-tts_amd/csrc/unit_ce.hip; host side msmctts_amd/hip/unit_ce.py
+ * masked_cross_entropy / unit_argmax).  Replaces the 'softmax' chain of MultiStageQuantizer.compute_embedding_loss, reference
+ * msmctts/networks/vqgantts/msmc_vqgan.py:254-258 with the masking of :266-268 -- cross_entropy(reduction='none'), masked_fill,
+ * sum, / sum of lengths -- which stores [N][K] fp32 log-probabilities and cannot take the -1 padding of unit labels.
+ * logits [B][T][ld], dtype 0 = fp32, 1 = bf16: the first K columns of a row are the classes, 1 <= K <= ld (ld: the width of a
+ * projection built wider than K).  target [B][T] int64; lengths [B] int32 (len_is_64 = 0) or int64.  Row (b, t) is VALID when
+ * t < lengths[b]; the logits of other rows are never read.  A valid row whose target is outside [0, K) is IGNORED: no loss, zero
+ * gradient.  The denominator is the sum of the lengths as given.  A wave per row, any K; 16-byte loads and stores where
+ * ld % (4 fp32 / 8 bf16) == 0 and logits (and glogits) are 16-byte aligned, element accesses otherwise -- the two paths add in
+ * different orders (both documented in the source's header) and may differ in the last bits.
+ * K < 1, K > ld, B < 1, T < 1, B T >= 2^31, another dtype or a NULL operand: MSMC_E_SHAPE, nothing launched, nothing written.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Bytes of the forward's scratch (one fp32 partial and one int count per workgroup, each array rounded up to 16 bytes); 0 for a
+ * refused B, T. */
+size_t msmc_unit_ce_workspace(int B, int T);
+
+/* Two launches.  lse [B][T] fp32 = m + logf(sum_k expf(x_k - m)), m the row maximum, on valid rows (0 elsewhere); pred [B][T]
+ * int64 (may be NULL) = the arg-max over the K classes, lowest index on ties (exact: comparisons only), -1 on padded rows;
+ * out[0] = (sum over valid, not ignored rows of lse - x[target]) / sum of lengths, out[1] = 1 / sum of lengths (for the backward
+ * pass); correct (int64[1], may be NULL) = the rows with pred == target.  sum of lengths <= 0: out[0] = out[1] = 0.
+ * Every sum runs in a fixed order (source header), no floating-point atomics: same inputs, same bits within one build.
+ * workspace 16-byte aligned, at least msmc_unit_ce_workspace(B, T) bytes: MSMC_E_WORKSPACE otherwise, nothing launched. */
+int msmc_unit_ce_fwd(const void* logits, int dtype, const int64_t* target, const void* lengths, int len_is_64, float* lse, int64_t* pred,
+                     float* out, int64_t* correct, void* workspace, size_t workspace_bytes, int B, int T, int K, int ld,
+                     msmc_stream stream);
+
+/* One launch.  glogits [B][T][ld] in the logits' dtype = (expf(x_k - lse) - [k == target]) * gout[0] * out[1] for k < K on valid,
+ * not ignored rows; +0 in the columns K .. ld - 1, on padded rows and on ignored rows.  Every element is written exactly once. */
+int msmc_unit_ce_bwd(const void* logits, int dtype, const int64_t* target, const void* lengths, int len_is_64, const float* lse,
+                     const float* out, const float* gout, void* glogits, int B, int T, int K, int ld, msmc_stream stream);
+
+/* The forward's arg-max alone (the same device function: the same labels): pred [B][T] int64, -1 on padded rows.  One launch. */
+int msmc_unit_argmax(const void* logits, int dtype, const void* lengths, int len_is_64, int64_t* pred, int B, int T, int K, int ld,
+                     msmc_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * G1/G2/D1/D2 channels-last implicit-GEMM convolution family on the matrix cores.
  * Replaces the cuDNN/MIOpen convolutions behind
  *   Generator.forward / ResBlock1.forward   reference msmctts/networks/hifigan/generator.py:40-55, common.py:44-51

@@ -57,6 +57,10 @@ _SIGNATURES = {
     'msmc_units_embed_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'msmc_units_embed_workspace': (_sz, [_i, _i, _i]),
     'msmc_units_embed_bwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    'msmc_unit_ce_workspace': (_sz, [_i, _i]),
+    'msmc_unit_ce_fwd': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    'msmc_unit_ce_bwd': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'msmc_unit_argmax': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from ...hip import losses as hiploss
 from ...hip import norm as hipnorm
+from ...hip import unit_ce as hipunitce
 from ...hip import vq as hipvq
 from ...hip.convnet import ConvBank, ConvLayer, hip_conv
 from ...utils.utils import get_mask_from_lengths
@@ -24,6 +25,15 @@ def _positions(lengths, device, width):
     ``lengths.max()`` (a host sync); the batch contract guarantees it equals the padded length."""
     pos = torch.arange(1, width + 1, device=device).unsqueeze(0).repeat(lengths.shape[0], 1)
     return pos.masked_fill(get_mask_from_lengths(lengths.to(device), width), 0)
+
+
+def _fused_softmax(p, target, lengths):
+    """the 'softmax' embedding loss runs as hip/unit_ce.py's ``masked_cross_entropy`` (GPU, or the interpreter in the CPU tests):
+    [B, T, K] fp32 / bf16 logits, device lengths, target indices [B, T] or [B, T, 1]"""
+    return (p.dim() == 3 and p.dtype in (torch.float32, torch.bfloat16) and hiploss.usable(p) and torch.is_tensor(lengths)
+            and lengths.device == p.device and lengths.dtype in (torch.int32, torch.int64) and torch.is_tensor(target)
+            and target.dtype == torch.int64 and target.device == p.device
+            and tuple(target.shape) in (tuple(p.shape[:2]), tuple(p.shape[:2]) + (1,)))
 
 
 def _fft_pos(lengths, feat):
@@ -149,6 +159,7 @@ class MultiStageQuantizer(nn.Module):
                 self.transposed_conv.append(nn.ConvTranspose1d(n_model_size, n_model_size, k, u, padding=(k - u) // 2))
         self.hip_dtype = torch.float32        # compute dtype of the HIP GEMMs (trainer: bfloat16 in bf16 runs)
         self.use_hip = True                # (False, set by hand: every layer of the quantiser on stock operators)
+        self.fused_softmax = True          # (False, set by hand: the 'softmax' embedding loss on the stock operator chain)
         self._bank = None
 
     # -- the 1x1 channel GEMMs, the prior predictor's WaveNet stack and their Tanh / gate on the gfx950 kernels ---------
@@ -263,6 +274,13 @@ class MultiStageQuantizer(nn.Module):
                         and lengths.device == p.device and lengths.dtype in (torch.int32, torch.int64)):
                     # mean over channels, masked sum over frames, / sum of lengths: one fused masked mean (two launches)
                     loss = hiploss.masked_mean(p, lengths, b=st['target_outputs'].detach())
+                    losses['embed_loss_%s_%d' % (method, i)] = loss
+                    parts.append(loss)
+                    pweights.append(weight)
+                    continue
+                if method == 'softmax' and self.fused_softmax and _fused_softmax(p, st['target_indices'], lengths):
+                    # cross-entropy per frame, masked sum, / sum of lengths: hip/unit_ce.py (no [N, K] log-probabilities)
+                    loss = hipunitce.masked_cross_entropy(p, st['target_indices'].detach().reshape(p.shape[:2]), lengths)
                     losses['embed_loss_%s_%d' % (method, i)] = loss
                     parts.append(loss)
                     pweights.append(weight)

@@ -44,6 +44,11 @@ that also adds the global embedding, and for the gradient a per-label sum follow
 frames, no nearest-centroid search, no ``in_linear`` over the frames.  Deviation from the frame path: padded rows (and rows whose
 label is outside [0, K)) of the decoder input are zeros there, where the frame path has whatever ``in_linear`` makes of the
 padding frames; the FFT blocks mask padded positions, so with a frame decoder the valid frames do not see the difference.
+
+The stage in front of the units (no reference counterpart either): ``KMeansVQGANEmb.compute_embedding_loss`` is the loss of a
+text -> unit predictor against this model (``trainers/unit_predictor_trainer.py``) -- ``'softmax'`` over the K centroids on
+csrc/unit_ce.hip, ``'mse'`` and the ``'triple*'`` methods as for the multi-stage quantiser -- and ``decode_units`` turns such a
+predictor's logits into the labels (or runs) ``synthesis_units`` takes.
 """
 import pickle
 
@@ -52,13 +57,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ...hip import losses as hiploss
 from ...hip import norm as hipnorm
+from ...hip import unit_ce as hipunitce
 from ...hip import window as hipwindow
 from ...hip.kmeans import fit_kmeans, kmeans_plusplus  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
 from ...hip import units as hipunits
 from ...hip import vq as hipvq
 from ...hip.units import assign_units, collapse_units, unit_usage, usage_summary  # noqa: F401  -- frames -> units on that file
 from ...hip.units import expand_units, unit_embed  # noqa: F401  -- and units -> the decoder input (``forward_units``)
+from ...utils.utils import get_mask_from_lengths
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
 from .modules import Quantize
@@ -342,10 +350,21 @@ class KMeansVQGANEmb(nn.Module):
             out['decoder_outputs'] = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
         return out
 
-    def synthesis_units(self, ind, length=None, ref=None, dur=None, ulen=None):
+    def synthesis_units(self, ind, length=None, *third, ref=None, dur=None, ulen=None):
         """``synthesis`` from stored labels.  Without ``dur``: ind [B, T] frame labels, ``length`` [B] (None: every frame).
         With ``dur`` [B, R]: ``ind`` holds the units of (unit, duration) runs, ``ulen`` [B] their number (None: every slot), and
-        the frame labels come from ``expand_units`` (one read-back to size them).  Returns what ``synthesis`` returns."""
+        the frame labels come from ``expand_units`` (one read-back to size them).  Returns what ``synthesis`` returns.
+        The runs also come positionally, ``synthesis_units(units, dur, ulen, ref=...)`` -- what ``decode_units(..., collapse=True)``
+        and ``collapse_units`` return: a two-dimensional second argument is the durations.  (Otherwise a third positional
+        argument is ``ref``, as it always was.)"""
+        if len(third) > 1:
+            raise TypeError('synthesis_units takes at most three positional arguments')
+        if torch.is_tensor(length) and length.dim() == 2 and dur is None:
+            dur, length = length, None
+            if third:
+                ulen = third[0]
+        elif third:
+            ref = third[0]
         if dur is not None:
             if ulen is None:
                 ulen = torch.full((ind.shape[0],), ind.shape[1], dtype=torch.int64, device=ind.device)
@@ -362,6 +381,62 @@ class KMeansVQGANEmb(nn.Module):
                 out['mel_outputs'] = self.mel_predictor(dec_in)
             return out
         return wav
+
+    def compute_embedding_loss(self, quantizer_outputs, quantizer_lengths, quantizer_states, methods=['mse'],
+                               loss_weights=[1.0]):
+        """The losses of a predictor of this model's units (no reference counterpart; signature and keys of
+        ``MSMCVQGANEmb.compute_embedding_loss``: ``embed_loss_<method>_0`` and ``total_loss``).  One stage: ``quantizer_outputs[0]``
+        [B, T, width] is the prediction, ``quantizer_states['quantizer_indices'][0]`` [B, T] the unit labels (-1 allowed on
+        padding), ``quantizer_lengths[0]`` the lengths.  Methods: ``'softmax'`` -- the prediction is logits whose first K columns
+        are the K centroids (a projection may be built wider), ``masked_cross_entropy`` (csrc/unit_ce.hip), which also leaves the
+        count of frames whose arg-max is the label in ``quantizer_states['unit_correct']`` (a 0-dim device tensor); ``'mse'`` -- against
+        ``quantizer_states['quantizer_outputs'][0]``, or the centroid rows of the labels where the states carry none; the
+        ``'triple*'`` methods -- ``Quantize.compute_triple_loss`` (the wide kernel at unit widths).  Every term is the masked sum over
+        valid frames divided by the sum of the lengths."""
+        q = self.quantizer.quantizer[0]
+        p, lengths = quantizer_outputs[0], quantizer_lengths[0]
+        ind = quantizer_states['quantizer_indices'][0].detach().reshape(p.shape[:2])
+        weights = loss_weights[0] if isinstance(loss_weights[0], (list, tuple)) else loss_weights
+        losses, parts, pweights = {}, [], []
+
+        def masked(loss):
+            loss = loss.masked_fill(get_mask_from_lengths(lengths.to(loss.device), loss.shape[1]), 0)
+            return loss.sum() / lengths.sum()
+        for method, weight in zip(methods, weights):
+            if method == 'softmax':
+                loss, correct = hipunitce.masked_cross_entropy(p, ind, lengths, classes=q.n_embed, return_correct=True)
+                if isinstance(quantizer_states, dict):
+                    quantizer_states['unit_correct'] = correct
+            elif method == 'mse':
+                frames = (quantizer_states.get('quantizer_outputs') or (None,))[0]
+                if frames is None:
+                    frames = q.embed_code(ind.clamp(0, q.n_embed - 1))
+                frames = frames.detach()
+                if (hiploss.usable(p) and p.dtype in (torch.float32, torch.bfloat16) and frames.dtype in (torch.float32, torch.bfloat16)
+                        and lengths.device == p.device and lengths.dtype in (torch.int32, torch.int64)):
+                    loss = hiploss.masked_mean(p, lengths, b=frames)
+                else:
+                    loss = masked(F.mse_loss(p, frames, reduction='none').mean(-1))
+            elif method in ('triple', 'triple_mean', 'triple_sum'):
+                # (a label outside [0, K) can only be padding: masked below, clamped so that the kernel reads a codeword)
+                loss = masked(q.compute_triple_loss(p, ind.clamp(0, q.n_embed - 1), reduction='sum' if method == 'triple_sum' else 'mean'))
+            else:
+                raise NotImplementedError('embedding loss %r' % method)
+            losses['embed_loss_%s_0' % method] = loss
+            parts.append(loss)
+            pweights.append(weight)
+        losses['total_loss'] = hiploss.weighted_sum(parts, pweights) if parts else 0
+        return losses
+
+    def decode_units(self, logits, length, collapse=False):
+        """A unit predictor's logits [B, T, width] (the first K columns are the K centroids) -> labels [B, T] int64, -1 behind
+        ``length`` (``unit_argmax``, csrc/unit_ce.hip); ``collapse``: the runs ``(units, dur, ulen)`` of ``collapse_units``
+        instead -- ``synthesis_units(*decode_units(logits, length, collapse=True), ref=...)`` is the waveform."""
+        length = torch.as_tensor(length).to(device=logits.device)
+        if length.dtype not in (torch.int32, torch.int64):
+            length = length.long()
+        labels = hipunitce.unit_argmax(logits, length, classes=self.quantizer.quantizer[0].n_embed)
+        return collapse_units(labels, length) if collapse else labels
 
     def analysis(self, emb, emb_length):
         if self.training:

@@ -67,6 +67,28 @@ def make_unit_batch(batch_size=16, frames=400, n_units=1000, mel_dim=80, hop=200
     return batch
 
 
+def make_text_unit_batch(batch_size=16, frames=400, n_units=1000, n_symbols=(100, 10, 2), phonemes=(30, 56), centers=None,
+                         seed=1234, rank=0, device='cpu'):
+    """A ``UnitPredictorTrainer`` batch: the text side of ``make_text_batch`` (``text``, ``text_length``, ``dur``: durations that
+    sum to the utterance's frames) and the unit labels of ``make_unit_batch`` (``units (B,T) int64`` uniform in [0, n_units) with
+    padding -1, ``units_length`` sorted descending with ``max == frames``).  With ``centers`` [K, d] (K >= n_units) the batch
+    carries the labels' frames instead -- ``emb (B,T,d)`` = the centroid rows of those same labels, zeros on padding, and
+    ``emb_length``: the batch a nearest-centroid search turns back into the unit batch."""
+    g = torch.Generator().manual_seed(seed + rank)
+    lengths = torch.randint(frames // 2, frames + 1, (batch_size,), generator=g)
+    lengths[0] = frames
+    lengths = torch.sort(lengths, descending=True).values.to(torch.int64)
+    units = torch.randint(0, n_units, (batch_size, frames), generator=g, dtype=torch.int64)
+    valid = torch.arange(frames)[None, :] < lengths[:, None]
+    batch = make_text_batch(lengths.tolist(), n_symbols=n_symbols, phonemes=phonemes, seed=seed + 1, rank=rank)
+    if centers is None:
+        batch.update(units=torch.where(valid, units, torch.full_like(units, -1)), units_length=lengths)
+    else:
+        rows = torch.as_tensor(centers, dtype=torch.float32)[units]
+        batch.update(emb=torch.where(valid[:, :, None], rows, torch.zeros_like(rows)), emb_length=lengths)
+    return {k: v.to(device) for k, v in batch.items()}
+
+
 def make_text_batch(mel_length, n_symbols=(100, 10, 2), phonemes=(30, 56), seed=4321, rank=0, device='cpu'):
     """The text side of a ``TTSDataset`` batch (reference msmctts/datasets/tts_dataset.py) for the given mel lengths:
     ``text (B, P, 3)`` symbol / tone / boundary ids (0 = padding), ``text_length (B,)``, ``dur (B, P)`` whole-frame durations of
