@@ -291,6 +291,44 @@ int msmc_units_embed_bwd(const float* gout, const int64_t* ind, const int64_t* l
                          size_t workspace_bytes, int B, int T, int C, int K, msmc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SE  the pitch / energy side encoder of MAMSEncoder (msmc-tts_amd/csrc/side_enc.hip; host side msmctts_amd/hip/side_enc.py
+ * side_front / pool_add).  Replaces, reference msmctts/networks/vqgantts/msmc_vqgan_emb.py:61-66 and :95-112, the torch.cat of
+ * the two tracks, the first Conv1d (P + E input channels: below the 8-channel granularity of the convolution kernels) with its
+ * Tanh, and per stage the transposes around avg_pool1d(ceil_mode=True) of the side encoding and the addition to the stage output.
+ * All tensors channels-last and contiguous.  Every sum runs in a fixed order (source header): no floating-point atomics, same
+ * inputs, same bits within one build.  A refused shape returns MSMC_E_SHAPE; nothing is launched, nothing written.
+ * ------------------------------------------------------------------------------------------- */
+
+/* y [B][T][C] (y_dtype 0 = fp32, 1 = bf16; 16-byte aligned) = tanhf(bias[c] + sum_ci sum_k w[c][ci][k] x[b][t + k - (taps-1)/2][ci]),
+ * x = 0 outside [0, T); input channel ci < P is pitch [B][T][P], the others energy [B][T][E] (fp32; a pointer may be NULL where
+ * its width is 0).  w [C][P + E][taps], bias [C]: nn.Conv1d's layout, fp32, accumulated in fp32.  No length masking.  One launch.
+ * Takes 1 <= P + E <= 8, taps odd and <= 15, C % 8 == 0, C (P + E) taps + C <= 12288 (the weight is staged in LDS). */
+int msmc_side_front_fwd(const float* pitch, const float* energy, const float* w, const float* bias, void* y, int y_dtype, int B, int T,
+                        int P, int E, int C, int taps, msmc_stream stream);
+
+/* Bytes of the backward's scratch: one set of (dw, db) partials per tile of 32 frames of an utterance; 0 for a refused shape. */
+size_t msmc_side_front_bwd_workspace(int B, int T, int P, int E, int C, int taps);
+
+/* dw [C][P + E][taps] and db [C] (fp32, overwritten) from y and gy [B][T][C] (both y_dtype): dz = gy (1 - y y) in fp32,
+ * dw = sum_{b,t} dz x, db = sum_{b,t} dz.  Two launches: per-tile partials, then their sum in ascending tile order.  No gradient
+ * to pitch / energy.  workspace 16-byte aligned, at least msmc_side_front_bwd_workspace bytes: MSMC_E_WORKSPACE otherwise. */
+int msmc_side_front_bwd(const float* pitch, const float* energy, const void* y, const void* gy, int y_dtype, float* dw, float* db,
+                        void* workspace, size_t workspace_bytes, int B, int T, int P, int E, int C, int taps, msmc_stream stream);
+
+/* side [B][Tin][C] fp32, feat [B][Tout][C] (feat_dtype 0 = fp32, 1 = bf16), Tout == ceil(Tin / scale), scale >= 1:
+ * pooled [B][Tout][C] fp32 = the mean of the in-bounds frames of window u (summed in ascending frame, divided by their count:
+ * avg_pool1d(kernel = stride = scale, ceil_mode = True, padding = 0)); out [B][Tout][C] in feat's dtype = feat + cast(pooled).
+ * scale == 1: out = feat + cast(side); pooled is not touched and may be NULL.  One launch. */
+int msmc_pool_add_fwd(const float* side, const void* feat, int feat_dtype, float* pooled, void* out, int B, int Tin, int Tout, int C,
+                      int scale, msmc_stream stream);
+
+/* gside [B][Tin][C] fp32 = (gout + gpooled)[b][t / scale][c] / (frames of that window); gout [B][Tout][C] in gout_dtype, gpooled
+ * [B][Tout][C] fp32; either may be NULL (not both).  Every element of gside is written once.  One launch.  (The gradient of
+ * feat is gout itself.) */
+int msmc_pool_add_bwd(const void* gout, int gout_dtype, const float* gpooled, float* gside, int B, int Tin, int Tout, int C, int scale,
+                      msmc_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * UC  the unit predictor's loss and label decoding (msmc-tts_amd/csrc/unit_ce.hip; host side msmctts_amd/hip/unit_ce.py
  * masked_cross_entropy / unit_argmax).  Replaces the 'softmax' chain of MultiStageQuantizer.compute_embedding_loss, reference
  * msmctts/networks/vqgantts/msmc_vqgan.py:254-258 with the masking of :266-268 -- cross_entropy(reduction='none'), masked_fill,

@@ -1,2 +1,2 @@
 from .msmc_vqgan import MSMCVQGAN
-from .msmc_vqgan_emb import KMeansVQGANEmb, MSMCVQGANEmb
+from .msmc_vqgan_emb import EmbVC, KMeansVQGANEmb, MSMCVQGANEmb

@@ -59,6 +59,7 @@ import torch.nn.functional as F
 
 from ...hip import losses as hiploss
 from ...hip import norm as hipnorm
+from ...hip import side_enc as hipside
 from ...hip import unit_ce as hipunitce
 from ...hip import window as hipwindow
 from ...hip.kmeans import fit_kmeans, kmeans_plusplus  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
@@ -66,6 +67,7 @@ from ...hip import units as hipunits
 from ...hip import vq as hipvq
 from ...hip.units import assign_units, collapse_units, unit_usage, usage_summary  # noqa: F401  -- frames -> units on that file
 from ...hip.units import expand_units, unit_embed  # noqa: F401  -- and units -> the decoder input (``forward_units``)
+from ...hip.convnet import ConvBank, ConvLayer, hip_conv
 from ...utils.utils import get_mask_from_lengths
 from ..acoustic_models.transformer import FFTBlocks
 from ..hifigan.generator import Generator as HifiGANGenerator
@@ -102,22 +104,71 @@ class MAMSEncoder(nn.Module):
                 nn.Conv1d(in_channels, in_channels, 3, padding=1), nn.Tanh(),
                 nn.Conv1d(in_channels, in_channels, 1))
 
+    # True: the side encoder runs on csrc/side_enc.hip (first layer + Tanh, pooling + addition) and the implicit-GEMM kernels (the
+    # three C -> C layers) wherever they take the operands; False on an instance keeps the stock chain (tests and the bench compare)
+    fused_side = True
+
+    def _side_bank(self):
+        """the three C -> C layers of the side encoder as plain layers of one small ConvBank (fp32, as the side encoder computes);
+        None where the convolution kernels refuse the width -- those layers then stay on stock operators"""
+        if not hasattr(self, '_mid'):
+            self._mid = None
+            mods = [self.pitch_encoder[i] for i in (2, 4, 6)]
+            if all(m.in_channels % 8 == 0 and m.out_channels % 8 == 0 for m in mods):
+                layers = [ConvLayer(m, 'conv', (1, m.kernel_size[0]), (1, 1), (1, 1), (0, m.padding[0]), plain=True) for m in mods]
+                self._mid = (ConvBank(layers), layers)
+        if self._mid is not None:
+            self._mid[0].prepare(torch.float32)
+        return self._mid
+
+    def _side_fused(self, pitch, energy):
+        """the side encoding [B, T, C] fp32, channels-last, or None where the kernels do not take the operands"""
+        if not self.fused_side:
+            return None
+        first = self.pitch_encoder[0]
+        width = lambda t: 0 if t is None else t.shape[-1]
+        if width(pitch) + width(energy) != first.in_channels or not hipside.front_usable(
+                pitch if width(pitch) else None, energy if width(energy) else None, first.weight):
+            return None
+        side = hipside.side_front(pitch, energy, first.weight, first.bias)
+        mid = self._side_bank()
+        if mid is None:
+            side = side.transpose(1, 2)
+            for m in list(self.pitch_encoder)[2:]:
+                side = m(side)
+            return side.transpose(1, 2).contiguous()
+        bank, layers = mid
+        for i, layer in enumerate(layers):
+            side = hip_conv(bank, layer, side.unsqueeze(1)).squeeze(1)
+            if i < 2:
+                side = hipnorm.tanh(side.contiguous())
+        return side
+
     def forward(self, emb, input_length, pitch=None, energy=None):
+        fused = False
         if self.use_pitch:
-            side = self.pitch_encoder(torch.cat((pitch, energy), dim=-1).transpose(1, 2).float()).transpose(1, 2)
+            side = self._side_fused(pitch, energy)
+            fused = side is not None
+            if not fused:
+                side = self.pitch_encoder(torch.cat((pitch, energy), dim=-1).transpose(1, 2).float()).transpose(1, 2)
         outputs, content = [], None
         feat, flen = emb, input_length
         for enc, scale in zip(self.encoders, self.downsample_scales):
             if scale > 1:
                 feat = F.avg_pool1d(feat.transpose(1, 2), kernel_size=scale, stride=scale, ceil_mode=True).transpose(1, 2)
-                if self.use_pitch:
+                if self.use_pitch and not fused:
                     side = F.avg_pool1d(side.transpose(1, 2), kernel_size=scale, stride=scale, ceil_mode=True).transpose(1, 2)
                 flen = torch.ceil(flen / scale).int()
             feat, _ = enc(feat, _fft_pos(flen, feat), lengths=flen)
             if not outputs:
                 content = feat
             if self.use_pitch:
-                feat = feat + side.to(feat.dtype)
+                if fused and hipside.pool_usable(side, feat, scale):
+                    side, feat = hipside.pool_add(side, feat, scale)       # (pooled for the next stage, stage output + pooled)
+                else:
+                    if fused and scale > 1:
+                        side = F.avg_pool1d(side.transpose(1, 2), kernel_size=scale, stride=scale, ceil_mode=True).transpose(1, 2)
+                    feat = feat + side.to(feat.dtype)
             outputs.append((feat, flen))
         return outputs, content
 
@@ -230,6 +281,69 @@ class MSMCVQGANEmb(nn.Module):
                    'target_indices': quantizer_states['quantizer_indices'][i],
                    'target_lengths': quantizer_lengths[i]} for i in range(len(quantizer_outputs))]
         return self.quantizer.compute_embedding_loss(states, methods, loss_weights)
+
+
+class EmbVC(nn.Module):
+    """the quantiser-free voice-conversion model (reference :472-628): ``in_linear`` -> ``MAMSEncoder`` (pitch / energy side
+    encoder added to every stage) -> + the global encoder's utterance embedding of ``ref`` (training: of ``mel``) -> frame decoder ->
+    optional ``mel_predictor`` -> HifiGAN, the decoder input being the LAST stage's output as it is.  Constructor keywords,
+    ``state_dict`` keys and output-dictionary keys (``encoder_outputs``, ``encoder_lengths``, ``content_representations``,
+    ``mel_outputs``, ``decoder_outputs``) are the reference's; ``forward`` also takes the ``window`` / ``window_frames`` forms of
+    ``MSMCVQGANEmb.forward``; the size refusals are ``MSMCVQGANEmb``'s.  The last stage must run at the input's frame rate
+    (``downsample_scales`` all 1 in the reference's use), or the global embedding, the frame decoder's positions and the windows
+    would not line up -- as in the reference.
+    The reference's ``analysis``, ``synthesis`` and ``compute_embedding_loss`` use a ``self.quantizer`` the class never creates
+    (:568, :587, :628) and cannot run; here they raise ``NotImplementedError`` naming the line."""
+
+    def __init__(self, emb_dim, n_model_size, pitch_dim=1, energy_dim=1, encoder_config=None, global_encoder_config=None,
+                 frame_decoder_config=None, decoder_config=None, pred_mel=False, mel_dim=None):
+        super().__init__()
+        self.in_linear = nn.Linear(emb_dim, n_model_size)
+        self.encoder = MAMSEncoder(n_model_size, pitch_dim=pitch_dim, energy_dim=energy_dim, **encoder_config)
+        if global_encoder_config is not None:
+            name = (global_encoder_config.get('_name') if isinstance(global_encoder_config, dict)
+                    else getattr(global_encoder_config, '_name', None))
+            if name != 'ECAPA_TDNN':
+                raise ValueError('Wrong global encoder: {}'.format(name))
+            self.global_encoder = ECAPA_TDNN(in_channels=mel_dim, embd_dim=n_model_size, channels=n_model_size)
+        decoder_config = dict(decoder_config)
+        decoder_config['num_mels'] = n_model_size
+        self.decoder = HifiGANGenerator(**decoder_config)
+        if frame_decoder_config is not None:
+            self.frame_decoder = FFTBlocks(d_model=n_model_size, name='frame_decoder', **frame_decoder_config)
+        if pred_mel:
+            self.mel_predictor = nn.Linear(n_model_size, mel_dim if mel_dim is not None else emb_dim)
+
+    _decode_frames = MSMCVQGANEmb._decode_frames
+    _frame_decode = MSMCVQGANEmb._frame_decode
+    _window = MSMCVQGANEmb._window
+
+    def forward(self, emb, emb_length, pitch=None, energy=None, mel=None, ref=None, window='full', window_frames=None):
+        """``window`` / ``window_frames`` as ``MSMCVQGANEmb.forward``"""
+        if self.training:
+            hipnorm.advance_seed(emb.device)
+        enc, content = self.encoder(self.in_linear(emb), emb_length, pitch, energy)
+        feats, lens = zip(*enc)
+        out = {'encoder_outputs': feats[::-1], 'encoder_lengths': lens[::-1], 'content_representations': content}
+        dec_in = self._decode_frames(feats[-1], emb_length, mel if ref is None else ref)
+        if hasattr(self, 'mel_predictor'):
+            out['mel_outputs'] = self.mel_predictor(dec_in)
+        if window is not None:
+            dec_in = self._window(dec_in, window, window_frames)
+            out['decoder_outputs'] = self.decoder(dec_in.transpose(1, 2)).transpose(1, 2)
+        return out
+
+    def analysis(self, emb, emb_length, pitch=None, energy=None):
+        raise NotImplementedError('EmbVC.analysis: the reference quantises with a self.quantizer the class never creates '
+                                  '(msmc_vqgan_emb.py:568) and cannot run; forward() returns the encoder outputs')
+
+    def synthesis(self, quantizer_outputs, quantizer_lengths, ref=None):
+        raise NotImplementedError('EmbVC.synthesis: the reference quantises with a self.quantizer the class never creates '
+                                  '(msmc_vqgan_emb.py:587) and cannot run; forward() decodes to the waveform')
+
+    def compute_embedding_loss(self, quantizer_outputs, quantizer_lengths, quantizer_states, methods=['mse'], loss_weights=[1.0]):
+        raise NotImplementedError('EmbVC.compute_embedding_loss: the reference calls a self.quantizer the class never creates '
+                                  '(msmc_vqgan_emb.py:628) and cannot run')
 
 
 def _load_centroids(path):

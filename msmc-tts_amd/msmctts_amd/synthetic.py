@@ -22,11 +22,13 @@ def make_batch(batch_size=16, frames=400, in_dim=80, hop=300, seed=1234, rank=0,
     return {k: v.to(device) for k, v in batch.items()}
 
 
-def make_emb_batch(batch_size=16, frames=400, emb_dim=1024, mel_dim=80, hop=200, seed=1234, rank=0, device='cpu'):
+def make_emb_batch(batch_size=16, frames=400, emb_dim=1024, mel_dim=80, hop=200, seed=1234, rank=0, device='cpu', tracks=False):
     """The contract of ``EmbDataset.collate_fn`` (``EmbVQGANTrainer.train_step``'s batch): ``emb (B,T,emb_dim)`` ~ N(0,1) with
     padding 0, ``emb_length (B,) int64`` sorted descending with ``max == T``, ``mel (B,T,mel_dim)`` ~ N(0,1) with padding -4,
     ``wav (B, T*hop, 1)`` ~ U(-1,1) with padding 0, ``wav_length = emb_length * hop``; ``emb_length_host`` is the host list of
-    the lengths the trainer samples its windows from (a loader hands it along; reading ``emb_length`` back would be a sync)."""
+    the lengths the trainer samples its windows from (a loader hands it along; reading ``emb_length`` back would be a sync).
+    ``tracks``: also ``pitch`` ~ N(0,1) and ``energy`` ~ U(0,1), (B,T,1) fp32 with padding 0 -- drawn from the same generator after
+    everything else, so the other entries keep their bits whatever the flag."""
     g = torch.Generator().manual_seed(seed + rank)
     lengths = torch.randint(frames // 2, frames + 1, (batch_size,), generator=g)
     lengths[0] = frames
@@ -40,6 +42,11 @@ def make_emb_batch(batch_size=16, frames=400, emb_dim=1024, mel_dim=80, hop=200,
     s = torch.arange(frames * hop)[None, :, None]
     wav = torch.where(s < (lengths * hop)[:, None, None], wav, torch.zeros_like(wav))
     batch = {'emb': emb, 'emb_length': lengths, 'mel': mel, 'wav': wav, 'wav_length': lengths * hop}
+    if tracks:
+        pitch = torch.randn(batch_size, frames, 1, generator=g)
+        energy = torch.rand(batch_size, frames, 1, generator=g)
+        batch['pitch'] = torch.where(valid, pitch, torch.zeros_like(pitch))
+        batch['energy'] = torch.where(valid, energy, torch.zeros_like(energy))
     batch = {k: v.to(device) for k, v in batch.items()}
     batch['emb_length_host'] = lengths.tolist()
     return batch

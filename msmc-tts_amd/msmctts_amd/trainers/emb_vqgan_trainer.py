@@ -19,7 +19,8 @@ A task whose autoencoder is ``KMeansVQGANEmb`` trains here as well, in all three
 ``encoder_indices`` but no ``encoder_diffs`` (its codebook is frozen and its input is data: a VQ term could train nothing), on
 which the reference's step fails with a ``KeyError``; here a model output without ``encoder_diffs`` takes no VQ term and the
 loss dictionary carries no VQ keys (one guarded branch in ``VQGANTrainer._segment_a``).  Outputs that have ``encoder_diffs``
-behave as before.
+behave as before.  ``EmbVC`` -- no quantiser: neither ``encoder_diffs`` nor ``encoder_indices`` -- takes the same branch; nothing in
+the step reads ``encoder_indices``.
 
 A batch of stored unit labels -- ``units`` int64 [B, T] with -1 padding and ``units_length`` in the place of ``emb`` /
 ``emb_length`` (``EmbDataset`` on ``indices/`` files, ``synthetic.make_unit_batch``) -- goes to the model's ``forward_units``

@@ -197,7 +197,7 @@ class VQGANTrainer(BaseTrainer):
             vq = self.vq_criterion(out)
             losses.update(vq)
             g_loss = vq['vq_loss']
-        else:                               # a frozen codebook over data (KMeansVQGANEmb): no VQ term, no VQ keys
+        else:                               # a frozen codebook over data (KMeansVQGANEmb) or no quantiser at all (EmbVC): no VQ term, no VQ keys
             g_loss = None
         if 'mel_outputs' in out:
             if _fused_masked(out['mel_outputs'], mel_length) and mel.dtype == torch.float32 and mel.is_contiguous():
