@@ -366,6 +366,26 @@ int msmc_unit_argmax(const void* logits, int dtype, const void* lengths, int len
                      msmc_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * CE  stage targets of the multi-stage quantiser from stored code indices (msmc-tts_amd/csrc/code_embed.hip; host side
+ * msmctts_amd/hip/code_embed.py code_gather; MultiStageQuantizer.embed_codes).  With a frozen codebook the quantised output of a
+ * stage is, head by head, a codebook row: this replaces, for a predictor step on stored codes, the frozen autoencoder's whole
+ * analysis (reference msmctts/trainers/emb_vqgan_trainer.py:202-210).  Forward only.
+ * ------------------------------------------------------------------------------------------- */
+
+/* out[b][t][h d + c] = embed_t[h][ind[b][t][h]][c] where t < length[b] and 0 <= ind[b][t][h] < K; the d channels of a head
+ * whose label is outside [0, K) are +0 (nothing is read for that head), and so is every row t >= length[b].
+ * ind [B][T][H] int32 (ind_i64 = 0) or int64 (1); length [B] int32 on the device (any value: <= 0 makes the utterance all
+ * zeros); embed_t [H][K][d] fp32, the layout msmc_vq_prepare writes; out [B][T][H d] fp32 (out_bf16 = 0) or bf16 (1: one
+ * rounding to nearest even).  One launch; every element of out is written exactly once with plain stores (no zero-fill, no
+ * atomics); a label is range-checked before it forms an address.  d % 4 == 0 with embed_t and out 16-byte aligned: 16-byte
+ * loads and stores (bf16 out: one 16-byte store per 8 channels where d % 8 == 0, else 8 bytes per 4 channels); any other d >= 1
+ * or alignment: one element per access, the same values.
+ * B < 1, T < 1, H < 1, d < 1, K < 1, a flag outside {0, 1}, a NULL operand or a row of 2^31 - 2048 pieces or more:
+ * MSMC_E_SHAPE, nothing launched, nothing written.  The caller guarantees the shapes above (contiguous). */
+int msmc_code_gather(const void* ind, int ind_i64, const int* length, const float* embed_t, void* out, int out_bf16,
+                     int B, int T, int H, int d, int K, msmc_stream stream);
+
+/* ---------------------------------------------------------------------------------------------
  * G1/G2/D1/D2 channels-last implicit-GEMM convolution family on the matrix cores.
  * Replaces the cuDNN/MIOpen convolutions behind
  *   Generator.forward / ResBlock1.forward   reference msmctts/networks/hifigan/generator.py:40-55, common.py:44-51

@@ -61,6 +61,7 @@ _SIGNATURES = {
     'msmc_unit_ce_fwd': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     'msmc_unit_ce_bwd': (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'msmc_unit_argmax': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    'msmc_code_gather': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     'msmc_side_front_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'msmc_side_front_bwd_workspace': (_sz, [_i, _i, _i, _i, _i, _i]),
     'msmc_side_front_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),

@@ -146,6 +146,11 @@ class MultiHeadQuantize(nn.Module):
             _ema(self, x3, ind.reshape(x3.shape[0], x3.shape[1], -1), input_length, embed, cs, ea)
         return quant, diff, rank if sort else ind
 
+    def embed_code(self, embed_id):
+        """embed_id [..., H] -> [..., dim]: every head's codeword, side by side (the reference's class has no such method;
+        ``Quantize.embed_code`` per head)"""
+        assert embed_id.shape[-1] == self.n_head, (tuple(embed_id.shape), self.n_head)
+        return torch.cat([q.embed_code(embed_id[..., h]) for h, q in enumerate(self.quantizers)], dim=-1)
 
     def compute_triple_loss(self, prd_quant, trg_quant, reduction='mean', margin=1e-6, adaptive_margin=False):
         """mean over heads of the per-head triple loss (reference modules.py:152-168); trg_quant [B, T, H] indices"""

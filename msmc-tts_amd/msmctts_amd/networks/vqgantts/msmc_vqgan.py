@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ...hip import code_embed as hipcode
 from ...hip import losses as hiploss
 from ...hip import norm as hipnorm
 from ...hip import unit_ce as hipunitce
@@ -305,6 +306,42 @@ class MultiStageQuantizer(nn.Module):
         losses['total_loss'] = hiploss.weighted_sum(parts, pweights) if parts else 0
         return losses
 
+    def _code_rows(self, stage, ind):
+        """the stage's codebook as ``vq_prepare`` lays it out, embed_t [H, K, d] fp32.  In eval mode it is prepared once and kept
+        while the codebook's storage and version counter are what they were; in training mode (the EMA update moves the codebook)
+        it is prepared at every call.  ``frames=0``: no shortlist image, only the rows are read."""
+        embed = self.quantizer[stage]._packed()[0]
+        if not hipcode.usable(ind, embed):                    # (host tensors without the interpreter build: the stock chain)
+            return embed.detach().transpose(1, 2).contiguous()
+        key = (embed.data_ptr(), embed._version, embed.device, tuple(embed.shape))
+        cache = self.__dict__.setdefault('_code_cache', {})
+        hit = cache.get(stage) if not self.training else None
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        embed_t, _ = hipvq.vq_prepare(embed.detach().contiguous(), frames=0)
+        if not self.training:
+            cache[stage] = (key, embed_t)
+        return embed_t
+
+    def embed_codes(self, indices, lengths, out_dtype=torch.float32):
+        """The quantiser's states from stored code indices (no reference counterpart): ``indices`` is what ``forward`` returns as
+        ``quantizer_indices`` -- per stage, coarse to fine, [B, T_i, H] (a single-head stage also [B, T_i]), any integer type --
+        ``lengths`` the per-stage lengths in the same order.  Returns ``quantizer_outputs`` (per stage [B, T_i, embedding_dims] in
+        ``out_dtype``: the code rows, one ``code_gather`` launch per stage, zeros on padded rows and for labels outside [0, K)),
+        ``quantizer_indices`` and ``quantizer_lengths`` as given: the three keys ``compute_embedding_loss`` and the predictor's
+        teacher forcing read.  No gradient: the rows are targets."""
+        indices, lengths = list(indices), list(lengths)
+        if len(indices) != len(self.quantizer) or len(lengths) != len(self.quantizer):
+            raise ValueError('%d index tensors and %d length tensors for %d stages' % (len(indices), len(lengths), len(self.quantizer)))
+        outs = []
+        for i, (ind, length) in enumerate(zip(indices, lengths)):
+            heads = getattr(self.quantizer[i], 'n_head', 1)
+            ind3 = ind.unsqueeze(-1) if ind.dim() == 2 and heads == 1 else ind
+            if ind3.dim() != 3 or ind3.shape[-1] != heads:
+                raise ValueError('stage %d: indices [B, T, %d] expected, got %s' % (i, heads, tuple(ind.shape)))
+            outs.append(hipcode.code_gather(ind3, length, self._code_rows(i, ind3), out_dtype))
+        return {'quantizer_outputs': tuple(outs), 'quantizer_indices': tuple(indices), 'quantizer_lengths': lengths}
+
 
 class MSMCVQGAN(nn.Module):
     def __init__(self, in_dim, n_model_size, encoder_config=None, quantizer_config=None, frame_decoder_config=None,
@@ -400,6 +437,12 @@ class MSMCVQGAN(nn.Module):
                     'encoder_indices': qs['quantizer_indices'], 'encoder_diffs': qs['quantizer_diffs'],
                     'decoder_diffs': qs['predictor_diffs'], 'quantizer_states': qs}
         return qs
+
+    def analysis_codes(self, indices, lengths):
+        """``analysis`` from stored code indices (eval mode only): see ``MSMCVQGANEmb.analysis_codes``"""
+        if self.training:
+            raise RuntimeError('analysis_codes needs a frozen codebook: call it in eval mode')
+        return self.quantizer.embed_codes(indices, lengths)
 
     def synthesis(self, quantizer_outputs, quantizer_lengths):
         qs = quantizer_outputs

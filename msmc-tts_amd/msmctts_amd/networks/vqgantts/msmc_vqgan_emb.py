@@ -49,6 +49,15 @@ The stage in front of the units (no reference counterpart either): ``KMeansVQGAN
 text -> unit predictor against this model (``trainers/unit_predictor_trainer.py``) -- ``'softmax'`` over the K centroids on
 csrc/unit_ce.hip, ``'mse'`` and the ``'triple*'`` methods as for the multi-stage quantiser -- and ``decode_units`` turns such a
 predictor's logits into the labels (or runs) ``synthesis_units`` takes.
+
+The stored-code path of the main model (no reference counterpart): ``MSMCVQGANEmb.analysis_codes`` / ``synthesis_codes`` take the
+``quantizer_indices`` a run of ``analysis`` produced (``tools/extract_codes.py`` stores them) in the place of frames and rebuild
+the per-stage ``quantizer_outputs`` with one gather per stage (csrc/code_embed.hip) -- what ``EmbPredictorTrainer`` trains a text
+front-end on without running the frozen encoder and search at every step.  Deviation from ``analysis``: that returns the search
+kernel's straight-through value ``o = x + (q - x)`` (csrc/vq_common.inc: x the quantiser's input, q the code row), which is
+the code row up to two fp32 roundings; ``analysis_codes`` returns the code row q itself.  In fp32
+``|o - q| <= 2^-24 (|x| + 2 |q|)`` element by element (the rounding of q - x is at most 2^-24 (|q| + |x|), that of the sum at
+most 2^-24 |o| ~ 2^-24 |q|).
 """
 import pickle
 
@@ -259,6 +268,15 @@ class MSMCVQGANEmb(nn.Module):
                     'decoder_diffs': qs['predictor_diffs'], 'quantizer_states': qs, 'content_representations': content}
         return qs
 
+    def analysis_codes(self, indices, lengths):
+        """What eval-mode ``analysis`` returns that a predictor step reads -- ``quantizer_outputs``, ``quantizer_indices``,
+        ``quantizer_lengths`` -- from the stored ``quantizer_indices`` (per stage, coarse to fine) and the per-stage lengths:
+        ``MultiStageQuantizer.embed_codes``, one gather per stage; no frames, no encoder, no search.  Eval mode only (the codebook
+        must be the one the indices were extracted with): ``RuntimeError`` in training mode."""
+        if self.training:
+            raise RuntimeError('analysis_codes needs a frozen codebook: call it in eval mode')
+        return self.quantizer.embed_codes(indices, lengths)
+
     def synthesis(self, quantizer_outputs, quantizer_lengths, ref=None):
         qs = quantizer_outputs
         if not isinstance(quantizer_outputs, dict):
@@ -273,6 +291,10 @@ class MSMCVQGANEmb(nn.Module):
                 out['mel_outputs'] = self.mel_predictor(dec_in)
             return out
         return wav
+
+    def synthesis_codes(self, indices, lengths, ref=None):
+        """``synthesis`` from stored code indices: the waveform of ``analysis_codes(indices, lengths)['quantizer_outputs']``"""
+        return self.synthesis(self.analysis_codes(indices, lengths)['quantizer_outputs'], lengths, ref)
 
     def compute_embedding_loss(self, quantizer_outputs, quantizer_lengths, quantizer_states, methods=['mse'],
                                loss_weights=[1.0]):

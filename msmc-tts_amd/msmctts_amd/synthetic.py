@@ -96,6 +96,46 @@ def make_text_unit_batch(batch_size=16, frames=400, n_units=1000, n_symbols=(100
     return {k: v.to(device) for k, v in batch.items()}
 
 
+def make_text_emb_batch(batch_size=16, frames=400, emb_dim=1024, n_symbols=(100, 10, 2), phonemes=(30, 56), n_codes=None,
+                        downsample_scales=(1, 4), n_heads=4, tracks=False, seed=1234, rank=0, device='cpu'):
+    """An ``EmbPredictorTrainer`` batch: the text side of ``make_text_batch`` (``text``, ``text_length``, ``dur``: durations that
+    sum to the utterance's frames) and, with ``n_codes=None``, frames -- ``emb (B,T,emb_dim)`` ~ N(0,1) with padding 0,
+    ``emb_length`` sorted descending with ``max == frames``, and with ``tracks`` also ``pitch`` ~ N(0,1) / ``energy`` ~ U(0,1),
+    (B,T,1) with padding 0.  With ``n_codes = K`` the batch carries stored codes instead: ``codes_0 .. codes_{S-1}``, stage 0 the
+    coarsest, ``(B, T_i, n_heads) int64`` uniform in [0, K) with padding -1, T_i and the valid lengths from ``frames`` / the
+    lengths by ``downsample_scales``' ``ceil`` chain (the finest stage is the frames' own rate when ``downsample_scales[0] == 1``);
+    ``codes_length`` the finest stage's lengths, ``codes_length_host`` their host list.  Lengths, text and durations are the same
+    in both forms."""
+    g = torch.Generator().manual_seed(seed + rank)
+    lengths = torch.randint(frames // 2, frames + 1, (batch_size,), generator=g)
+    lengths[0] = frames
+    lengths = torch.sort(lengths, descending=True).values.to(torch.int64)
+    batch = make_text_batch(lengths.tolist(), n_symbols=n_symbols, phonemes=phonemes, seed=seed + 1, rank=rank)
+    if n_codes is None:
+        valid = torch.arange(frames)[None, :, None] < lengths[:, None, None]
+        emb = torch.randn(batch_size, frames, emb_dim, generator=g)
+        batch.update(emb=torch.where(valid, emb, torch.zeros_like(emb)), emb_length=lengths)
+        if tracks:
+            pitch = torch.randn(batch_size, frames, 1, generator=g)
+            energy = torch.rand(batch_size, frames, 1, generator=g)
+            batch.update(pitch=torch.where(valid, pitch, torch.zeros_like(pitch)),
+                         energy=torch.where(valid, energy, torch.zeros_like(energy)))
+        return {k: v.to(device) for k, v in batch.items()}
+    width, flen, stages = frames, lengths, []
+    for i, scale in enumerate(downsample_scales):
+        if i > 0 and scale > 1:
+            width, flen = -(-width // scale), torch.ceil(flen / scale).long()
+        codes = torch.randint(0, n_codes, (batch_size, width, n_heads), generator=g, dtype=torch.int64)
+        valid = torch.arange(width)[None, :, None] < flen[:, None, None]
+        stages.append(torch.where(valid, codes, torch.full_like(codes, -1)))
+    for i, codes in enumerate(stages[::-1]):
+        batch['codes_%d' % i] = codes
+    batch['codes_length'] = lengths
+    batch = {k: v.to(device) for k, v in batch.items()}
+    batch['codes_length_host'] = lengths.tolist()
+    return batch
+
+
 def make_text_batch(mel_length, n_symbols=(100, 10, 2), phonemes=(30, 56), seed=4321, rank=0, device='cpu'):
     """The text side of a ``TTSDataset`` batch (reference msmctts/datasets/tts_dataset.py) for the given mel lengths:
     ``text (B, P, 3)`` symbol / tone / boundary ids (0 = padding), ``text_length (B,)``, ``dur (B, P)`` whole-frame durations of

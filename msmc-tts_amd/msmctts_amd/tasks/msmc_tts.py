@@ -74,6 +74,21 @@ class NASynTTSEmb(MSMCTTS):
         out = self.autoencoder(**{k: v for k, v in input_dict.items() if k in ('emb', 'emb_length', 'pitch', 'energy', 'ref')})
         return {'wav': out['decoder_outputs'].squeeze(-1)}
 
+    def predict(self, input_dict):
+        """text (+ durations) -> per-stage features -> waveform, as the parent's; an autoencoder with a ``global_encoder`` gets
+        ``input_dict['ref']`` (the reference utterance's mel frames) for its ``synthesis``, which asserts that it is there.  The
+        predictor's feed leaves out the autoencoder's inputs (``ref``, ``emb``, ``emb_length``, ``pitch``, ``energy``)."""
+        if not hasattr(self.autoencoder, 'global_encoder'):
+            return super().predict(input_dict)
+        feed = {k: v for k, v in input_dict.items() if k not in ('mel', 'mel_length', 'ref', 'emb', 'emb_length', 'pitch', 'energy')}
+        out = self.predictor(**feed)
+        feats, lengths = out['feat'], out['feat_length']
+        wavs = self.autoencoder.synthesis(feats, lengths, input_dict.get('ref'))[..., 0]
+        wav_lengths = (lengths[-1] * wavs.shape[1] / feats[-1].shape[1]).int()
+        out['wav'] = [w[:n] for w, n in zip(wavs, wav_lengths)]
+        out['embedding'] = feats[-1]
+        return out
+
 
 class TTS(MSMCTTS):
     """``task._name: TTS`` resolves to the same container (its acoustic-model + vocoder pipeline is out of scope)."""
