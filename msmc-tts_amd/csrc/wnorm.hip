@@ -983,7 +983,8 @@ int msmc_lrelu_bwd_multi(const void* const* g, const void* const* y, void* const
     bool vec = true;
     for (int k = 0; k < n; ++k) {
         if (!g[k] || !y[k] || !gx[k] || nelem[k] <= 0) return MSMC_E_SHAPE;
-        vec = vec && (nelem[k] % VEC) == 0;
+        // (the 16-byte kernel needs whole vectors and that alignment of every operand: a contiguous view may start anywhere)
+        vec = vec && (nelem[k] % VEC) == 0 && (((size_t)g[k] | (size_t)y[k] | (size_t)gx[k]) & 15) == 0;
     }
     LreluMultiArgs a;
     a.n = n;

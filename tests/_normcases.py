@@ -90,15 +90,17 @@ DTYPES = ((0, torch.float32, 'fp32'), (1, torch.bfloat16, 'bf16'))
 
 
 # ---- helpers -------------------------------------------------------------------------------------------------------------------------
-def held(what, case, got, ref, bound):
-    """|got - ref| <= bound element by element (a NaN in ``got`` fails); records the largest share of the bound used"""
+def held(what, case, got, ref, bound, book=None):
+    """|got - ref| <= bound element by element (a NaN in ``got`` fails); records the largest share of the bound used.  ``book``:
+    another module's (MEASURED, FLOOR_HELD, print prefix) in place of this one's"""
+    measured, _, prefix = book or (MEASURED, FLOOR_HELD, 'norm')
     got, err = got.double(), (got.double() - ref).abs()
     assert not bool(torch.isnan(got).any()), '%s %s: an element was not written' % (what, case)
     bound = bound.expand_as(err)
     pos = bound > 0
     used = float((err[pos] / bound[pos]).max()) if bool(pos.any()) else 0.0
-    MEASURED.append((what, case, used, 'bound'))
-    print('norm %-26s %-34s share of the bound used %.3f' % (what, case, used))
+    measured.append((what, case, used, 'bound'))
+    print('%s %-26s %-34s share of the bound used %.3f' % (prefix, what, case, used))
     bad = ~(err <= bound)
     assert not bool(bad.any()), '%s %s: %d elements outside the bound, worst err %.3e at bound %.3e' % (
         what, case, int(bad.sum()), float(err[bad].max()), float(bound[bad][err[bad].argmax()]))
@@ -112,10 +114,11 @@ def half_ulp(ref, dtype):
     return torch.where(ref == 0, torch.zeros_like(ref), torch.ldexp(torch.ones_like(ref), e - 9))
 
 
-def yard(what, case, got, t32, ref, floor=None, half=None):
+def yard(what, case, got, t32, ref, floor=None, half=None, book=None):
     """the yardstick rule in both norms, ``half`` (the bf16 half-ulp of the output) added to the bar; a comparison that misses it
     passes only if it is listed in FLOOR_HELD (or torch's chain is exact) and every element lies inside ``floor + half`` (the
-    module docstring)"""
+    module docstring).  ``book``: as for ``held``"""
+    measured, floor_held, prefix = book or (MEASURED, FLOOR_HELD, 'norm')
     got, ref = got.double(), ref.double()
     assert not bool(torch.isnan(got).any()), '%s %s: an element was not written' % (what, case)
     half = torch.zeros_like(ref) if half is None else half
@@ -128,7 +131,7 @@ def yard(what, case, got, t32, ref, floor=None, half=None):
     how = 'yardstick'
     if not ok:
         assert floor is not None, '%s %s: %.2f x the fp32 chain and no derived bound' % (what, case, worst)
-        assert (what, case) in FLOOR_HELD or float(e32.max()) == 0.0, \
+        assert (what, case) in floor_held or float(e32.max()) == 0.0, \
             '%s %s: %.2f x the fp32 chain, and the case is not one of those held by the derived bound' % (what, case, worst)
         bound = floor.expand_as(err) + half
         inside = err <= bound
@@ -136,8 +139,8 @@ def yard(what, case, got, t32, ref, floor=None, half=None):
         how = 'floor %.3f' % used
         assert bool(inside.all()), '%s %s: %.2f x the fp32 chain and %d elements outside the derived bound (share %.2f)' % (
             what, case, worst, int((~inside).sum()), used)
-    MEASURED.append((what, case, worst, how))
-    print('norm %-26s %-34s %7.2f x torch fp32 of %.0f allowed  (%s)' % (what, case, worst, RATIO, how))
+    measured.append((what, case, worst, how))
+    print('%s %-26s %-34s %7.2f x torch fp32 of %.0f allowed  (%s)' % (prefix, what, case, worst, RATIO, how))
 
 
 class Out(object):
