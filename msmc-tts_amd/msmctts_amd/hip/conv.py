@@ -20,7 +20,6 @@ from . import lib
 _DT = {torch.float32: 0, torch.bfloat16: 1}
 
 
-
 class Geometry(object):
     """Forward geometry of conv(kernel (kh,kw), stride, dilation, padding) on an (Hin, Win) image."""
 
@@ -72,6 +71,7 @@ _GATHER_CANDIDATES = tuple((v, 0) for v in (1, 2, 3, 4, 5, 8, 9, 16, 17, 18, 19,
 # (round 6: (3, 0), (3, -2), (3, 1) and the first generation (1, 0) left the candidates: never chosen over configurations 1-5;
 #  the third generation stays reachable through its one chosen split and as wgrad5's fallback)
 _WGRAD_CANDIDATES = ((4, 0), (4, -1), (9, 0), (9, -1), (7, 0), (8, 0), (3, -1), (2, 0), (2, -1), (2, 1))
+_SPLIT_CANDIDATES = ((36, 0), (37, 0))
 TUNED = {}                                    # (kind, shape signature) -> (variant, split_shift, {candidate: ms})
 TUNE_CACHE = os.environ.get('MSMC_TUNE_CACHE', os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                             'tuned_gfx950.json'))
@@ -192,47 +192,103 @@ def _bounded(cache, limit=4096):
         cache.clear()
 
 
-def _tune(kind, desc, launch, candidates):
-    """Time ``launch()`` under every candidate (variant, split_shift); leave the fastest in the descriptor."""
-    desc._tuned = True
+def _capturing():
+    return torch.cuda.is_current_stream_capturing()
+
+
+def _may_time(budgeted=True):
+    """timing launches may be issued now: switched on, budget left, not on the interpreter, not inside a hipGraph capture"""
+    return AUTOTUNE and not lib._host_pointers_ok and (not budgeted or TUNE_BUDGET[0] > 0) and not _capturing()
+
+
+def _time_ms(fn):
+    """milliseconds per call of ``fn``, over three calls between two events (the caller has issued one validating call)"""
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(3):
+        fn()
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e) / 3.0
+
+
+def _tune(kind, desc, launch, candidates, on_trust=False):
+    """The one place that decides which (variant, split_shift) a descriptor of ``kind`` ('gather', 'gather-split', 'wgrad')
+    gets; afterwards ``desc._tuned`` is set and ``desc._borrowed`` says whether the fields are a neighbour's choice that no
+    launch has validated yet.  ``launch()`` issues the descriptor as it stands and returns the library's code.  ``on_trust``
+    is the one difference between the two kinds of call: a forward / data-gradient / split-GEMM launch may be issued once
+    more to validate a borrowed choice (the output is simply written twice); a weight gradient accumulates into dW, so its
+    borrowed choice is taken on trust and validated by the caller's real launch (``_wgrad`` falls back to (0, 0) once), and
+    its ``launch`` accumulates into scratch.
+
+    situation                        | forward / data gradient / split GEMM        | weight gradient (``on_trust``)
+    ---------------------------------+---------------------------------------------+--------------------------------------------
+    interpreter bound                | descriptor keeps the variant it was built   | same
+    (lib._host_pointers_ok)          | with; no lookup, no launch; marked tuned    |
+    exact key in TUNED               | decision applied; no timing launch; budget  | same; _borrowed false
+                                     | untouched                                   |
+    no exact key; TUNE_BORROW; a     | nearest (by log pixel count) applied, then  | a neighbour with variant >= 3 is ignored
+    tuned shape of the same class    | one validating launch.  Code 0: kept,       | when the descriptor is not bf16 (*);
+    exists                           | nothing written to TUNED, budget untouched. | otherwise it is applied with no extra
+                                     | Otherwise the previous fields are restored  | launch and _borrowed is true (the caller
+                                     | and the next row applies.                   | resets to (0, 0) and retries once if the
+                                     |                                             | real launch fails)
+    nothing found and (AUTOTUNE off, | library heuristic (fields as built); marked | same
+    or budget <= 0, or the stream is | tuned                                       |
+    capturing)                       |                                             |
+    nothing found, timing allowed    | budget minus 1; for every candidate in list | the same, with ``launch`` accumulating into
+                                     | order: one validating launch, skipped on a  | freshly zeroed scratch of max(1, dw_copies)
+                                     | non-zero code, then 3 timed launches; the   | copies and never into the caller's dW / db
+                                     | minimum wins, (0, 0) if none ran;           |
+                                     | TUNED[sig] = (variant, shift, {cand: ms})   |
+
+    (*) kept from the code this replaces: when timing is allowed, such an ignored neighbour is first tried like a forward
+    borrow -- one validating launch into scratch, kept on code 0 (the fp32 kernel ignores every variant but 3, which it
+    refuses), no TUNED entry, budget untouched, _borrowed false -- and only a refusal goes on to the timing row."""
+    desc._tuned, desc._borrowed = True, False
     if lib._host_pointers_ok:
         return
     sig = (kind,) + _signature(desc)
     hit = TUNED.get(sig)
     if hit is None:
         near = _nearest_tuned(sig)
-        if near is not None:        # borrowed from the nearest tuned shape of the same class (validated below)
+        if near is not None and on_trust and (near[0] < 3 or desc.dtype == 1):      # (generations 3 and up are bf16-only)
+            desc.variant, desc.split_shift, desc._borrowed = near[0], near[1], True
+            return
+        if near is not None and (not on_trust or _may_time()):
             keep = (desc.variant, desc.split_shift)
             desc.variant, desc.split_shift = near[0], near[1]
             if launch() == 0:
                 return
             desc.variant, desc.split_shift = keep
-    if hit is None and (not AUTOTUNE or TUNE_BUDGET[0] <= 0 or torch.cuda.is_current_stream_capturing()):
-        return                      # no timing launches now: library heuristic for this shape
-    if hit is None:
+        if not _may_time():
+            return                      # no timing launches now: library heuristic for this shape
         TUNE_BUDGET[0] -= 1
         times = {}
         for variant, shift in candidates:
             desc.variant, desc.split_shift = variant, shift
-            if launch() != 0:
-                continue
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(3):
-                launch()
-            e.record()
-            e.synchronize()
-            times[(variant, shift)] = s.elapsed_time(e) / 3.0
+            if launch() == 0:
+                times[(variant, shift)] = _time_ms(launch)
         best = min(times, key=times.get) if times else (0, 0)
         hit = TUNED[sig] = (best[0], best[1], times)
     desc.variant, desc.split_shift = hit[0], hit[1]
 
 
-def _gather(desc, stream, what):
+def _tuned_gather(desc, stream, kind='gather'):
+    """``desc`` with its kernel chosen (first use of a forward / data-gradient / split-GEMM descriptor)"""
     if not getattr(desc, '_tuned', False):
         fn = lib.get().msmc_conv_gather
-        _tune('gather', desc, lambda: fn(ctypes.byref(desc), stream), _GATHER_CANDIDATES)
-    lib.call('msmc_conv_gather', ctypes.byref(desc), stream, what=what)
+        _tune(kind, desc, lambda: fn(ctypes.byref(desc), stream), _SPLIT_CANDIDATES if kind == 'gather-split' else _GATHER_CANDIDATES)
+    return desc
+
+
+def _gather(desc, stream, what):
+    lib.call('msmc_conv_gather', ctypes.byref(_tuned_gather(desc, stream)), stream, what=what)
+
+
+def _snapshot(desc, stream):
+    """by-value copy of a (tuned) descriptor: grouped calls may meet the same cached descriptor twice"""
+    return lib.ConvDesc.from_buffer_copy(_tuned_gather(desc, stream))
 
 
 # -- deferred second stage of the no-atomics weight gradients ------------------------------------------------------------
@@ -307,43 +363,48 @@ def _workspace(device, stream, nbytes):
     return t.data_ptr(), t.numel() * 4
 
 
-def _wgrad(desc, g_ptr, dw, db, stream, what, seen=None):
-    L = lib.get()
+def _with_partials(defer, device, stream, need, members, call):
+    """``call(workspace, bytes)`` with room for ``need`` bytes of split partial results: a region of the armed arena, in which
+    case the launches inside run their first stage only and record the second (``DeferredReduce``), else the stream's scratch"""
+    if defer is not None and need and defer.n + members <= defer.CAPACITY:
+        ws = defer.take(device, need)
+        defer.begin()
+        try:
+            return call(ws, need)
+        finally:
+            defer.end()
+    return call(*_workspace(device, stream, need))
 
-    def fn(dref, gp, dwp, dbp, st, defer=None):
-        need = L.msmc_conv_wgrad_workspace(dref, gp)
-        if defer is not None and need and defer.n < defer.CAPACITY:
-            wsp = defer.take(dw.device, need)
-            defer.begin()
-            try:
-                return L.msmc_conv_wgrad_ws(dref, gp, dwp, dbp, wsp, need, st)
-            finally:
-                defer.end()
-        wsp, wsb = _workspace(dw.device, st, need) if need else (None, 0)
-        return L.msmc_conv_wgrad_ws(dref, gp, dwp, dbp, wsp, wsb, st)
-    dbp = db.data_ptr() if db is not None else None
-    defer = DEFER_TO if DEFER else None
+
+def _zeroed_targets(descs, device, with_db=True):
+    """fresh zeroed stand-ins for the dW / db of ``descs``: timing launches accumulate, so they never see the caller's"""
+    sdw = [torch.zeros(max(1, d.dw_copies) * d.ntaps * d.Cout * d.Cin, dtype=torch.float32, device=device) for d in descs]
+    sdb = [torch.zeros(max(1, d.dw_copies) * d.Cout, dtype=torch.float32, device=device) if with_db else None for d in descs]
+    return sdw, sdb
+
+
+def _wgrad(desc, g_ptr, dw, db, stream, what, seen=None):
+    L, dref = lib.get(), ctypes.byref(desc)
+
+    def launch(dwp, dbp, defer=None):
+        need = L.msmc_conv_wgrad_workspace(dref, g_ptr)
+        return _with_partials(defer, dw.device, stream, need, 1,
+                              lambda ws, nbytes: L.msmc_conv_wgrad_ws(dref, g_ptr, dwp, dbp, ws, nbytes, stream))
+    dwp, dbp = _operand(dw, contiguous=False, aligned=False), _operand(db, contiguous=False, aligned=False)
     if not getattr(desc, '_tuned', False):
-        cached = TUNED.get(('wgrad',) + _signature(desc)) if not lib._host_pointers_ok else None
-        if cached is None and not lib._host_pointers_ok:
-            cached = _nearest_tuned(('wgrad',) + _signature(desc))
-            if cached is not None and cached[0] >= 3 and desc.dtype != 1:
-                cached = None                 # (the third and fourth generations are bf16-only)
-        if cached is not None:
-            desc._borrowed = ('wgrad',) + _signature(desc) not in TUNED
-            desc.variant, desc.split_shift, desc._tuned = cached[0], cached[1], True
-        elif AUTOTUNE and TUNE_BUDGET[0] > 0 and not lib._host_pointers_ok and not torch.cuda.is_current_stream_capturing():
-            R = max(1, desc.dw_copies)                       # candidates accumulate into scratch, not into dW
-            sdw = torch.zeros(R * desc.ntaps * desc.Cout * desc.Cin, dtype=torch.float32, device=dw.device)
-            sdb = torch.zeros(R * desc.Cout, dtype=torch.float32, device=dw.device) if db is not None else None
-            sdbp = sdb.data_ptr() if sdb is not None else None
-            _tune('wgrad', desc, lambda: fn(ctypes.byref(desc), g_ptr, sdw.data_ptr(), sdbp, stream), _WGRAD_CANDIDATES)
-        else:
-            desc._tuned = True
-    rc = fn(ctypes.byref(desc), g_ptr, dw.data_ptr(), dbp, stream, defer)
+        scratch = []                                         # made when the tuner issues its first launch, if it does
+
+        def timing():
+            if not scratch:
+                scratch.extend(_zeroed_targets([desc], dw.device, db is not None))
+            (sdw,), (sdb,) = scratch                         # (allocated here, on the device of the checked dW)
+            return launch(sdw.data_ptr(), sdb.data_ptr() if sdb is not None else None)
+        _tune('wgrad', desc, timing, _WGRAD_CANDIDATES, on_trust=True)
+    defer = DEFER_TO if DEFER else None
+    rc = launch(dwp, dbp, defer)
     if rc != 0 and getattr(desc, '_borrowed', False):        # a neighbour's choice this shape cannot run: library heuristic
         desc.variant, desc.split_shift, desc._borrowed = 0, 0, False
-        rc = fn(ctypes.byref(desc), g_ptr, dw.data_ptr(), dbp, stream, defer)
+        rc = launch(dwp, dbp, defer)
     if seen is not None:
         seen.add(int(desc.variant))           # (ConvBank: layers whose weight gradients never use atomics need no privatised copies)
     if rc != 0:
@@ -352,38 +413,32 @@ def _wgrad(desc, g_ptr, dw, db, stream, what, seen=None):
                                          desc.Win, desc.Cin, desc.Hout, desc.Wout, desc.Cout, desc.ntaps))
 
 
-
-def _ptr(t):
-    """data pointer of a tensor the caller has validated (dtype, contiguity); GPU-only unless the kernel
-    interpreter is bound."""
+def _operand(t, dtype=None, contiguous=True, aligned=True):
+    """Data pointer of an optional tensor on its way into a descriptor or a pointer array (None stays None).  GPU-only unless
+    the kernel interpreter is bound; by default contiguous and 16-byte aligned (the kernels use vector accesses), of ``dtype``
+    where one is given."""
     if t is None:
         return None
     if not (t.is_cuda or lib._host_pointers_ok):
         raise RuntimeError('msmc HIP ops run on the GPU only (got a %s tensor); there is no CPU path' % t.device)
-    if not t.is_contiguous():
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError('msmc HIP ops: operand of dtype %s where %s is expected (epilogue operands share the activation dtype)'
+                         % (t.dtype, dtype))
+    if contiguous and not t.is_contiguous():
         raise ValueError('msmc HIP ops take contiguous tensors')
-    if t.data_ptr() % 16:
+    if aligned and t.data_ptr() % 16:
         raise ValueError('msmc HIP ops take 16-byte aligned operands (got an offset view)')
     return t.data_ptr()
 
 
-def _fill(desc_unused, x, w, out, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, taps, pad_mode, bias=None, mask_src=None,
-          res=None, res2=None, in_slope=1.0, mask_slope=1.0, out_div=1.0, out_slope=1.0, kind='gather'):
-    """Descriptor for one launch.  The geometry part is built once per distinct (shape, lattice, taps, flags) and
-    cached -- per call only the seven pointers change (the step issues ~2000 convolution launches, so the
-    host cost of a launch matters as much as its GPU time)."""
-    # ``kind``: a weight gradient and a data gradient of one transposed convolution share every geometry field, but
-    # their descriptors carry DIFFERENT kernel choices (desc.variant means another thing to msmc_conv_wgrad)
-    key = (kind, x.dtype, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, tuple(taps), pad_mode, in_slope, mask_slope, out_div,
-           out_slope)
-    desc = _PLANS.get(key)
-    if desc is None:
-        _bounded(_PLANS)
-        desc = _PLANS[key] = _build_desc(x.dtype, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, taps, pad_mode,
-                                         in_slope, mask_slope, out_div, out_slope)
-    desc.x, desc.w, desc.out = _ptr(x), _ptr(w), _ptr(out)
-    desc.bias, desc.mask_src, desc.res, desc.res2 = _ptr(bias), _ptr(mask_src), _ptr(res), _ptr(res2)
-    return desc
+def _pointers(tensors, **demands):
+    """``void*[]`` of a list of optional tensors, each through ``_operand``"""
+    return (ctypes.c_void_p * len(tensors))(*[_operand(t, **demands) for t in tensors])
+
+
+def _chunks(seq, n):
+    """``seq`` in pieces of at most ``n``: 16 members per grouped convolution call, 6 tensors per fold / leaky-ReLU launch"""
+    return [seq[i:i + n] for i in range(0, len(seq), n)]
 
 
 def _build_desc(dtype, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, taps, pad_mode, in_slope, mask_slope, out_div,
@@ -403,27 +458,29 @@ def _build_desc(dtype, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, taps, pad_mo
     return desc
 
 
+def _fill(x, w, out, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, taps, pad_mode, bias=None, mask_src=None,
+          res=None, res2=None, in_slope=1.0, mask_slope=1.0, out_div=1.0, out_slope=1.0, kind='gather'):
+    """Descriptor for one launch.  The geometry part is built once per distinct (shape, lattice, taps, flags) and
+    cached -- per call only the seven pointers change (the step issues ~2000 convolution launches, so the
+    host cost of a launch matters as much as its GPU time)."""
+    # ``kind``: a weight gradient and a data gradient of one transposed convolution share every geometry field, but
+    # their descriptors carry DIFFERENT kernel choices (desc.variant means another thing to msmc_conv_wgrad)
+    key = (kind, x.dtype, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, tuple(taps), pad_mode, in_slope, mask_slope, out_div,
+           out_slope)
+    desc = _PLANS.get(key)
+    if desc is None:
+        _bounded(_PLANS)
+        desc = _PLANS[key] = _build_desc(x.dtype, B, Hin, Win, Cin, Hout, Wout, Cout, lattice, taps, pad_mode,
+                                         in_slope, mask_slope, out_div, out_slope)
+    desc.x, desc.w, desc.out = _operand(x), _operand(w), _operand(out)
+    desc.bias, desc.mask_src, desc.res, desc.res2 = _operand(bias), _operand(mask_src), _operand(res), _operand(res2)
+    return desc
+
+
 def _check(x, w, *others):
     assert x.dtype in _DT and w.dtype == x.dtype, (x.dtype, w.dtype)
     for t in others:
         assert t is None or (t.dtype == x.dtype and t.is_contiguous()), 'epilogue operands share the activation dtype'
-
-
-def _dev_ok(t):
-    if not (t.is_cuda or lib._host_pointers_ok):
-        raise RuntimeError('msmc HIP ops run on the GPU only (got a %s tensor); there is no CPU path' % t.device)
-    if not t.is_contiguous():
-        raise ValueError('msmc HIP ops take contiguous tensors')
-    if t.data_ptr() % 16:
-        raise ValueError('msmc HIP ops take 16-byte aligned operands (got an offset view)')
-
-
-def _opt_ptr(t, like):
-    if t is None:
-        return None
-    if t.dtype != like.dtype or not t.is_contiguous() or t.data_ptr() % 16:
-        raise ValueError('epilogue operands share the activation dtype, are contiguous and 16-byte aligned')
-    return t.data_ptr()
 
 
 def _forward_desc(x, w, geom, bias=None, in_slope=1.0, res=None, res2=None, out_div=1.0, out_slope=1.0):
@@ -439,11 +496,11 @@ def _forward_desc(x, w, geom, bias=None, in_slope=1.0, res=None, res2=None, out_
                            1 if geom.reflect else 0, in_slope, 1.0, out_div, out_slope)
         plan = geom.plans[key] = (desc, (B, geom.Hout, geom.Wout, Cout))
     desc, oshape = plan
-    _dev_ok(x)
+    # (weights and bias may be views into packed parameter buffers: no layout demand on them)
+    desc.x, desc.w, desc.bias = _operand(x), _operand(w, contiguous=False, aligned=False), _operand(bias, contiguous=False, aligned=False)
+    desc.res, desc.res2, desc.mask_src = _operand(res, x.dtype), _operand(res2, x.dtype), None
     out = torch.empty(oshape, dtype=x.dtype, device=x.device)
-    desc.x, desc.w, desc.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    desc.bias = bias.data_ptr() if bias is not None else None
-    desc.res, desc.res2, desc.mask_src = _opt_ptr(res, x), _opt_ptr(res2, x), None
+    desc.out = _operand(out)
     return desc, out
 
 
@@ -454,13 +511,8 @@ def conv_forward(x, w, geom, bias=None, in_slope=1.0, res=None, res2=None, out_d
     return out
 
 
-_SPLIT_CANDIDATES = ((36, 0), (37, 0))
-
-
-def const_gemm_split(x, wimg, cout):
-    """x [B, 1, T, Cin] fp32 times a CONSTANT matrix given as its pre-split bf16 image (hip/spectral.py split_image:
-    [cout][chunks of 32 values][hi 32 | lo 32]) -> [B, 1, T, cout] fp32: three bf16 matrix-core products with fp32
-    accumulation (csrc/gemm1.inc conv_gemm1s_kernel, variants 36 / 37 -- 128- or 64-row tiles, timed once per shape)."""
+def _split_desc(x, wimg, cout, stream):
+    """tuned descriptor (pointers filled in) and output tensor of one split constant GEMM"""
     B, _, T, Cin = x.shape
     assert x.dtype == torch.float32 and wimg.dtype == torch.bfloat16 and wimg.shape[0] == cout and wimg.is_contiguous()
     assert wimg.shape[1] * 32 >= Cin and wimg.shape[2] == 64, (tuple(wimg.shape), Cin)
@@ -471,15 +523,19 @@ def const_gemm_split(x, wimg, cout):
         desc = _PLANS[key] = _build_desc(torch.float32, B, 1, T, Cin, 1, T, cout, (1, T, 0, 1, 0, 1, 1, 1, 0, 0), ((0, 0, 0),), 0,
                                          1.0, 1.0, 1.0, 1.0)
         desc.variant = 37 if ((B * T + 127) // 128) * ((cout + 127) // 128) < 192 else 36
-    _dev_ok(x)
-    _dev_ok(wimg)
+    desc.x, desc.w = _operand(x), _operand(wimg)
     out = torch.empty((B, 1, T, cout), dtype=torch.float32, device=x.device)
-    desc.x, desc.w, desc.out = x.data_ptr(), wimg.data_ptr(), out.data_ptr()
+    desc.out = _operand(out)
     desc.bias = desc.res = desc.res2 = desc.mask_src = None
+    return _tuned_gather(desc, stream, 'gather-split'), out
+
+
+def const_gemm_split(x, wimg, cout):
+    """x [B, 1, T, Cin] fp32 times a CONSTANT matrix given as its pre-split bf16 image (hip/spectral.py split_image:
+    [cout][chunks of 32 values][hi 32 | lo 32]) -> [B, 1, T, cout] fp32: three bf16 matrix-core products with fp32
+    accumulation (csrc/gemm1.inc conv_gemm1s_kernel, variants 36 / 37 -- 128- or 64-row tiles, timed once per shape)."""
     stream = lib.stream(x)
-    if not getattr(desc, '_tuned', False):
-        fn = lib.get().msmc_conv_gather
-        _tune('gather-split', desc, lambda: fn(ctypes.byref(desc), stream), _SPLIT_CANDIDATES)
+    desc, out = _split_desc(x, wimg, cout, stream)
     lib.call('msmc_conv_gather', ctypes.byref(desc), stream, what='msmc_conv_gather(split constant GEMM)')
     return out
 
@@ -488,40 +544,15 @@ def const_gemm_split_group(xs, wimgs, couts):
     """``const_gemm_split`` of several independent (x, matrix image) pairs as ONE grouped call: members of one tile width share a
     grid (csrc/gemm1.inc conv_gemm1s_group_kernel) -- the five resolution front-ends' DFT (or filter-bank) GEMMs in one launch"""
     assert 0 < len(xs) <= 16
-    snaps, outs = [], []
     stream = lib.stream(xs[0])
+    snaps, outs = [], []
     for x, wimg, cout in zip(xs, wimgs, couts):
-        B, _, T, Cin = x.shape
-        assert x.dtype == torch.float32 and wimg.dtype == torch.bfloat16 and wimg.shape[0] == cout and wimg.is_contiguous()
-        assert wimg.shape[1] * 32 >= Cin and wimg.shape[2] == 64, (tuple(wimg.shape), Cin)
-        key = ('g1s', B, T, Cin, cout)
-        desc = _PLANS.get(key)
-        if desc is None:
-            _bounded(_PLANS)
-            desc = _PLANS[key] = _build_desc(torch.float32, B, 1, T, Cin, 1, T, cout, (1, T, 0, 1, 0, 1, 1, 1, 0, 0), ((0, 0, 0),), 0,
-                                             1.0, 1.0, 1.0, 1.0)
-            desc.variant = 37 if ((B * T + 127) // 128) * ((cout + 127) // 128) < 192 else 36
-        _dev_ok(x)
-        _dev_ok(wimg)
-        out = torch.empty((B, 1, T, cout), dtype=torch.float32, device=x.device)
-        desc.x, desc.w, desc.out = x.data_ptr(), wimg.data_ptr(), out.data_ptr()
-        desc.bias = desc.res = desc.res2 = desc.mask_src = None
-        if not getattr(desc, '_tuned', False):
-            fn = lib.get().msmc_conv_gather
-            _tune('gather-split', desc, lambda: fn(ctypes.byref(desc), stream), _SPLIT_CANDIDATES)
+        desc, out = _split_desc(x, wimg, cout, stream)
         snaps.append(lib.ConvDesc.from_buffer_copy(desc))
         outs.append(out)
     arr = (lib.ConvDesc * len(snaps))(*snaps)
     lib.call('msmc_conv_gather_group', arr, len(snaps), stream, what='msmc_conv_gather_group(split constant GEMMs)')
     return outs
-
-
-def _snapshot(desc, stream):
-    """by-value copy of a (tuned) descriptor: grouped calls may meet the same cached descriptor twice"""
-    if not getattr(desc, '_tuned', False):
-        fn = lib.get().msmc_conv_gather
-        _tune('gather', desc, lambda: fn(ctypes.byref(desc), stream), _GATHER_CANDIDATES)
-    return lib.ConvDesc.from_buffer_copy(desc)
 
 
 _GROUP_CODES = {'single': 0, 'group': 1, 'group4': 2, 'uniform': 3}
@@ -535,31 +566,24 @@ def _group_choice(kind, snaps, grouped_fn, single_fn, group4_fn=None, uniform_fn
     members on grids of their own (``group4_fn``, weight gradients only), (3, v): grouped with variant v imposed on every
     member (``uniform_fn(v)`` returns the launcher or None when a member refuses v; forward / data gradients only).
     Timed once per member-shape combination (grouping fills the chip for small grids but imposes one kernel
-    instantiation on all members).  Returns (code, variant)."""
+    instantiation on all members); the launchers are called only then.  Returns (code, variant)."""
     if len(snaps) == 1:
         return 0, 0
     if lib._host_pointers_ok:
         return 1, 0
     sig = (kind,) + tuple(_signature(d) + (d.variant, d.split_shift) for d in snaps)
     hit = TUNED.get(sig)
-    if hit is None and (not AUTOTUNE or torch.cuda.is_current_stream_capturing()):
-        return 1, 0
     if hit is None:
+        if not _may_time(budgeted=False):
+            return 1, 0
         times = {}
         options = [(('group', 0), grouped_fn), (('single', 0), single_fn), (('group4', 0), group4_fn)]
         if uniform_fn is not None and len(set(d.variant for d in snaps)) > 1:
             options += [(('uniform', v), uniform_fn(v)) for v in _UNIFORM_CANDIDATES]
         for name, fn in options:
-            if fn is None:
-                continue
-            fn()
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(3):
+            if fn is not None:
                 fn()
-            e.record()
-            e.synchronize()
-            times[name] = s.elapsed_time(e) / 3.0
+                times[name] = _time_ms(fn)
         best = min(times, key=times.get)
         hit = TUNED[sig] = (_GROUP_CODES[best[0]], best[1], times)
     return hit[0], hit[1]
@@ -576,7 +600,7 @@ def _group_choice(kind, snaps, grouped_fn, single_fn, group4_fn=None, uniform_fn
 GROUP_PHASES = os.environ.get('MSMC_GROUP_PHASES', '1') != '0'            # stride phases of a transposed convolution as one grouped call
 
 
-def _gather_group(snaps, stream, what, device=None):
+def _gather_group(snaps, stream, what):
     """independent launches issued together (msmc_conv_gather_group) when that is the faster way for these shapes"""
     def single():
         for d in snaps:
@@ -617,7 +641,7 @@ def conv_forward_group(items):
         desc, out = _forward_desc(**it)
         snaps.append(_snapshot(desc, stream))
         outs.append(out)
-    _gather_group(snaps, stream, 'msmc_conv_gather_group', items[0]['x'].device)
+    _gather_group(snaps, stream, 'msmc_conv_gather_group')
     return outs
 
 
@@ -653,10 +677,10 @@ def _dgrad_descs(g, wb, geom, mask_src=None, mask_slope=1.0, res=None, out_div=1
                                       1.0), ry, rx))
         plan = geom.plans[key] = (descs, (B, Hx, Wx, Cin))
     descs, oshape = plan
-    _dev_ok(g)
+    gp, wp = _operand(g), _operand(wb, contiguous=False, aligned=False)
+    mp, rp = _operand(mask_src, g.dtype), _operand(res, g.dtype)
     gx = torch.empty(oshape, dtype=g.dtype, device=g.device)
-    gp, wp, op = g.data_ptr(), wb.data_ptr(), gx.data_ptr()
-    mp, rp = _opt_ptr(mask_src, g), _opt_ptr(res, g)
+    op = _operand(gx)
     live = []
     for desc, ry, rx in descs:
         if desc is None:                      # phase that no kernel tap reaches: gradient is the epilogue of zero
@@ -690,8 +714,8 @@ def conv_dgrad_group(items):
         live, gx = _dgrad_descs(**it)
         snaps.extend(_snapshot(d, stream) for d in live)
         outs.append(gx)
-    for i in range(0, len(snaps), 16):                   # msmc_conv_gather_group carries at most 16 members
-        _gather_group(snaps[i:i + 16], stream, 'msmc_conv_gather_group(dgrad)', items[0]['g'].device)
+    for part in _chunks(snaps, 16):
+        _gather_group(part, stream, 'msmc_conv_gather_group(dgrad)')
     return outs
 
 
@@ -708,16 +732,15 @@ def conv_transpose1d_forward(x, w, k, stride, padding, bias=None, in_slope=1.0):
         assert taps1, 'kernel_size >= stride expected'
         taps = [(0, off, kk) for off, kk in taps1]
         lattice = (1, n, 0, 1, r, stride, 1, 1, 0, 0)
-        d = _fill(None, x, w, out, B, 1, Lin, Cin, 1, Lout, Cout, lattice, taps, 0, bias=bias,
-                  in_slope=in_slope)
+        d = _fill(x, w, out, B, 1, Lin, Cin, 1, Lout, Cout, lattice, taps, 0, bias=bias, in_slope=in_slope)
         if not GROUP_PHASES:
             _gather(d, stream, 'msmc_conv_gather(convT)')
         else:
             snaps.append(_snapshot(d, stream))
     # the stride phases write disjoint output positions: independent launches, issued like the members of a grouped call
     # (one grid where their kernel choices coincide, parallel branches otherwise) instead of back to back
-    for i in range(0, len(snaps), 16):
-        _gather_group(snaps[i:i + 16], stream, 'msmc_conv_gather_group(convT)', x.device)
+    for part in _chunks(snaps, 16):
+        _gather_group(part, stream, 'msmc_conv_gather_group(convT)')
     return out
 
 
@@ -730,15 +753,14 @@ def conv_transpose1d_dgrad(g, wb, k, stride, padding, Lin, mask_src=None, mask_s
     gx = torch.empty((B, 1, Lin, Cin), dtype=g.dtype, device=g.device)
     taps = [(0, kk, kk) for kk in range(k)]
     lattice = (1, Lin, 0, 1, 0, 1, 1, stride, 0, -padding)
-    d = _fill(None, g, wb, gx, B, 1, Lout, Cout, 1, Lin, Cin, lattice, taps, 0, mask_src=mask_src, res=res,
+    d = _fill(g, wb, gx, B, 1, Lout, Cout, 1, Lin, Cin, lattice, taps, 0, mask_src=mask_src, res=res,
               mask_slope=mask_slope, out_div=out_div)
     _gather(d, lib.stream(g), 'msmc_conv_gather(convT dgrad)')
     return gx
 
 
-def conv_wgrad(x, g, geom, n_slices, in_slope=1.0, dw=None, db=None, copies=1, seen=None):
-    """dW [kh*kw, Cout, Cin] fp32 of ``conv_forward`` (x [B,Hin,Win,Cin] pre-activation, g [B,Hout,Wout,Cout]);
-    when ``db`` (fp32 [Cout]) is given the bias gradient is accumulated into it by the same launch."""
+def _wgrad_desc(x, g, geom, in_slope, copies):
+    """descriptor (pointers filled in; the gradient operand ``g`` travels beside it) of one weight gradient"""
     key = ('w', x.dtype, x.shape[0], x.shape[3], g.shape[3], in_slope)
     desc = geom.plans.get(key)
     if desc is None:
@@ -748,13 +770,19 @@ def conv_wgrad(x, g, geom, n_slices, in_slope=1.0, dw=None, db=None, copies=1, s
         desc = geom.plans[key] = _build_desc(x.dtype, B, Hin, Win, Cin, geom.Hout, geom.Wout, g.shape[3],
                                              geom.fwd_lattice, geom.fwd_taps, 1 if geom.reflect else 0, in_slope, 1.0,
                                              1.0, 1.0)
-    _dev_ok(x)
-    _dev_ok(g)
-    if dw is None:
-        dw = torch.zeros((n_slices, g.shape[3], x.shape[3]), dtype=torch.float32, device=x.device)
-    desc.x = desc.w = desc.out = x.data_ptr()
+    desc.x = desc.w = desc.out = _operand(x)
+    _operand(g)
     desc.bias = desc.mask_src = desc.res = desc.res2 = None
     desc.dw_copies = copies              # dw / db then hold ``copies`` privatised accumulators back to back
+    return desc
+
+
+def conv_wgrad(x, g, geom, n_slices, in_slope=1.0, dw=None, db=None, copies=1, seen=None):
+    """dW [kh*kw, Cout, Cin] fp32 of ``conv_forward`` (x [B,Hin,Win,Cin] pre-activation, g [B,Hout,Wout,Cout]);
+    when ``db`` (fp32 [Cout]) is given the bias gradient is accumulated into it by the same launch."""
+    desc = _wgrad_desc(x, g, geom, in_slope, copies)
+    if dw is None:
+        dw = torch.zeros((n_slices, g.shape[3], x.shape[3]), dtype=torch.float32, device=x.device)
     _wgrad(desc, g.data_ptr(), dw, db, lib.stream(x), 'msmc_conv_wgrad', seen)
     return dw
 
@@ -762,85 +790,59 @@ def conv_wgrad(x, g, geom, n_slices, in_slope=1.0, dw=None, db=None, copies=1, s
 def conv_wgrad_group(items):
     """``items``: list of dicts with the arguments of ``conv_wgrad`` (``dw`` required): independent weight gradients
     issued as grouped launches (msmc_conv_wgrad_group)."""
-    stream = lib.stream(items[0]['x'])
-    snaps, gs, dws, dbs = [], [], [], []
+    stream, device = lib.stream(items[0]['x']), items[0]['x'].device
+    members = []                              # (descriptor by value, g, dw, db) of the members whose kernel is chosen
     for it in items:
         x, g, geom = it['x'], it['g'], it['geom']
         in_slope, dw, db, copies = it.get('in_slope', 1.0), it['dw'], it.get('db'), it.get('copies', 1)
-        key = ('w', x.dtype, x.shape[0], x.shape[3], g.shape[3], in_slope)
-        desc = geom.plans.get(key)
-        if desc is None or not getattr(desc, '_tuned', False):
-            conv_wgrad(x, g, geom, it['n_slices'], in_slope=in_slope, dw=dw, db=db, copies=copies, seen=it.get('seen'))   # builds + tunes
+        desc = _wgrad_desc(x, g, geom, in_slope, copies)
+        if not getattr(desc, '_tuned', False):
+            conv_wgrad(x, g, geom, it['n_slices'], in_slope=in_slope, dw=dw, db=db, copies=copies, seen=it.get('seen'))   # tunes
             continue
-        _dev_ok(x)
-        _dev_ok(g)
-        desc.x = desc.w = desc.out = x.data_ptr()
-        desc.bias = desc.mask_src = desc.res = desc.res2 = None
-        desc.dw_copies = copies
         if it.get('seen') is not None:
             it['seen'].add(int(desc.variant))
-        snaps.append(lib.ConvDesc.from_buffer_copy(desc))
-        gs.append(g.data_ptr())
-        dws.append(dw.data_ptr())
-        dbs.append(db.data_ptr() if db is not None else None)
+        members.append((lib.ConvDesc.from_buffer_copy(desc), g, dw, db))
     L = lib.get()
-    for i in range(0, len(snaps), 16):
-        part = snaps[i:i + 16]
+    defer = DEFER_TO if DEFER else None
+    for chunk in _chunks(members, 16):
+        part = [m[0] for m in chunk]
         n = len(part)
         arr = (lib.ConvDesc * n)(*part)
-        vp = ctypes.c_void_p * n
-        ga, dwa, dba = vp(*gs[i:i + 16]), vp(*dws[i:i + 16]), vp(*dbs[i:i + 16])
-
+        ga = _pointers([m[1] for m in chunk])
+        real = [_pointers([m[i] for m in chunk], contiguous=False, aligned=False) for i in (2, 3)]
         needs = [L.msmc_conv_wgrad_workspace(ctypes.byref(part[k]), ga[k]) for k in range(n)]
         need = sum(needs)
-        wsp, wsb = _workspace(items[0]['x'].device, stream, need) if need else (None, 0)
-        defer = DEFER_TO if DEFER else None
 
-        def deferred(call):
-            """the real (not a timing) issue of this group: first stage only, partial results into the arena"""
-            nonlocal wsp, wsb
-            if defer is None or not need or defer.n + n > defer.CAPACITY:
-                return call()
-            keep = (wsp, wsb)
-            wsp, wsb = defer.take(items[0]['x'].device, need), need
-            defer.begin()
-            try:
-                return call()
-            finally:
-                defer.end()
-                wsp, wsb = keep
-
-        def grouped():
-            lib.call('msmc_conv_wgrad_group_ws', arr, ga, dwa, dba, n, wsp, wsb, stream)
-
-        def grouped4():
-            lib.call('msmc_conv_wgrad_group_ws4', arr, ga, dwa, dba, n, wsp, wsb, stream, 1)
-
-        g4 = grouped4 if sum(1 for d in part if d.variant >= 4) > 1 else None
-
-        def single():
+        # launchers: (dW array, db array, workspace, workspace bytes) -- the timing pass binds them to scratch, the real issue
+        # to the members' own targets
+        def single(dwa, dba, ws, nbytes):
             off = 0                                   # (members get regions of their own: a deferred second stage reads
             for k in range(n):                        #  them all at the end of the backward pass)
-                lib.call('msmc_conv_wgrad_ws', ctypes.byref(part[k]), ga[k], dwa[k], dba[k], (wsp + off) if needs[k] else None,
+                lib.call('msmc_conv_wgrad_ws', ctypes.byref(part[k]), ga[k], dwa[k], dba[k], (ws + off) if needs[k] else None,
                          needs[k], stream)
                 off += needs[k]
 
-        if n == 1:
-            deferred(single)
-            continue
-        # the timing launches accumulate into the real dW / db: harmless only on scratch, so time on copies
-        if AUTOTUNE and not lib._host_pointers_ok and not torch.cuda.is_current_stream_capturing():
-            sig = ('wgrad-group',) + tuple(_signature(d) + (d.variant, d.split_shift) for d in part)
-            if sig not in TUNED:
-                keep = (dwa, dba)
-                scratch = [torch.zeros(max(1, d.dw_copies) * d.ntaps * d.Cout * d.Cin, dtype=torch.float32,
-                                       device=items[0]['x'].device) for d in part]
-                sb = [torch.zeros(max(1, d.dw_copies) * d.Cout, dtype=torch.float32, device=items[0]['x'].device)
-                      for d in part]
-                dwa, dba = vp(*[t.data_ptr() for t in scratch]), vp(*[t.data_ptr() for t in sb])
-                _group_choice('wgrad-group', part, grouped, single, g4)
-                dwa, dba = keep
-        deferred((single, grouped, g4 or grouped)[_group_choice('wgrad-group', part, grouped, single, g4)[0]])
+        def grouped(dwa, dba, ws, nbytes):
+            lib.call('msmc_conv_wgrad_group_ws', arr, ga, dwa, dba, n, ws, nbytes, stream)
+
+        def grouped4(dwa, dba, ws, nbytes):
+            lib.call('msmc_conv_wgrad_group_ws4', arr, ga, dwa, dba, n, ws, nbytes, stream, 1)
+
+        g4 = grouped4 if sum(1 for d in part if d.variant >= 4) > 1 else None
+        scratch = []                                  # made when the tuner issues its first launch, if it does
+
+        def timing(launcher):
+            """``launcher`` accumulating into zeroed copies of the targets, partial results in the stream's scratch"""
+            def run():
+                if not scratch:
+                    scratch.extend(_zeroed_targets(part, device))
+                launcher(_pointers(scratch[0]), _pointers(scratch[1]), *_workspace(device, stream, need))
+            return launcher and run
+
+        code = _group_choice('wgrad-group', part, timing(grouped), timing(single), timing(g4))[0]
+        launcher = (single, grouped, g4 or grouped)[code]
+        # the real issue: first stage only, partial results into the arena, where a DeferredReduce is armed
+        _with_partials(defer, device, stream, need, n, lambda ws, nbytes: launcher(real[0], real[1], ws, nbytes))
 
 
 def conv_transpose1d_wgrad(x, g, k, stride, padding, in_slope=1.0, dw=None, copies=1, seen=None):
@@ -855,11 +857,10 @@ def conv_transpose1d_wgrad(x, g, k, stride, padding, in_slope=1.0, dw=None, copi
     taps = [(0, kk, kk) for kk in range(k)]
     lattice = (1, Lin, 0, 1, 0, 1, 1, stride, 0, -padding)
     # kernel roles: "x" = g (fine, channels Cout), "g" = x (coarse, channels Cin) -> dw[k][Cin][Cout]
-    d = _fill(None, g, g, g, B, 1, Lout, Cout, 1, Lin, Cin, lattice, taps, 0, in_slope=1.0,
-              mask_slope=in_slope, kind='wgrad')
-    lib.ptr(dw, torch.float32)
+    d = _fill(g, g, g, B, 1, Lout, Cout, 1, Lin, Cin, lattice, taps, 0, in_slope=1.0, mask_slope=in_slope, kind='wgrad')
+    _operand(dw, torch.float32, aligned=False)
     d.dw_copies = copies
-    _wgrad(d, lib.ptr(x), dw, None, lib.stream(x), 'msmc_conv_wgrad(convT)', seen)
+    _wgrad(d, _operand(x, aligned=False), dw, None, lib.stream(x), 'msmc_conv_wgrad(convT)', seen)
     return dw
 
 
@@ -877,14 +878,13 @@ def colsum(g2d, out=None):
     return out
 
 
-
 def reflect_fold(gp, H, W, p=1, mask_src=None, slope=1.0):
     """Backward of ReflectionPad2d(p) (+ leaky-ReLU' mask): gp [B,H+2p,W+2p,C] -> gx [B,H,W,C]."""
     B, C = gp.shape[0], gp.shape[3]
     assert gp.shape[1:3] == (H + 2 * p, W + 2 * p) and gp.is_contiguous()
     gx = torch.empty((B, H, W, C), dtype=gp.dtype, device=gp.device)
-    lib.call('msmc_reflect_fold', lib.ptr(gp), lib.ptr(mask_src) if mask_src is not None else None, lib.ptr(gx), B, H, W, C, p,
-             float(slope), _DT[gp.dtype], lib.stream(gp))
+    lib.call('msmc_reflect_fold', lib.ptr(gp), lib.ptr(mask_src), lib.ptr(gx), B, H, W, C, p, float(slope), _DT[gp.dtype],
+             lib.stream(gp))
     return gx
 
 
@@ -899,19 +899,14 @@ def lrelu_bwd(g, y, slope):
 def lrelu_bwd_group(pairs, slope):
     """[(g, y), ...] -> [g * (y > 0 ? 1 : slope), ...] in launches of up to six tensors (msmc_lrelu_bwd_multi)."""
     outs = []
-    for i in range(0, len(pairs), 6):
-        part = pairs[i:i + 6]
-        n = len(part)
-        gxs = []
+    for part in _chunks(pairs, 6):
+        n, lead = len(part), part[0][0]
         for g, y in part:
-            assert g.shape == y.shape and g.dtype == y.dtype == part[0][0].dtype and g.is_contiguous() and y.is_contiguous()
-            _dev_ok(g)
-            _dev_ok(y)
-            gxs.append(torch.empty_like(g))
-        vp = ctypes.c_void_p * n
-        lib.call('msmc_lrelu_bwd_multi', vp(*[g.data_ptr() for g, _ in part]), vp(*[y.data_ptr() for _, y in part]),
-                 vp(*[t.data_ptr() for t in gxs]), (ctypes.c_long * n)(*[g.numel() for g, _ in part]), n, float(slope),
-                 _DT[part[0][0].dtype], lib.stream(part[0][0]))
+            assert g.shape == y.shape and g.dtype == y.dtype == lead.dtype and g.is_contiguous() and y.is_contiguous()
+        gs, ys = _pointers([g for g, _ in part]), _pointers([y for _, y in part])
+        gxs = [torch.empty_like(g) for g, _ in part]
+        lib.call('msmc_lrelu_bwd_multi', gs, ys, _pointers(gxs), (ctypes.c_long * n)(*[g.numel() for g, _ in part]), n,
+                 float(slope), _DT[lead.dtype], lib.stream(lead))
         outs.extend(gxs)
     return outs
 
@@ -922,26 +917,19 @@ def reflect_fold_group(items, p=1, slope=1.0, tap_first=False):
     activated map and res the gradient of its other reader (msmc_reflect_fold_multi_tap)."""
     items = [tuple(it) + (None,) * (5 - len(it)) for it in items]
     outs = []
-    for i in range(0, len(items), 6):
-        part = items[i:i + 6]
-        n = len(part)
-        gxs, masks, ress = [], [], []
+    for part in _chunks(items, 6):
+        n, lead = len(part), part[0][0]
+        gxs = []
         for gp, H, W, mask, res in part:
-            assert gp.shape[1:3] == (H + 2 * p, W + 2 * p) and gp.is_contiguous() and gp.dtype == part[0][0].dtype
-            _dev_ok(gp)
+            assert gp.shape[1:3] == (H + 2 * p, W + 2 * p) and gp.is_contiguous() and gp.dtype == lead.dtype
             gx = torch.empty((gp.shape[0], H, W, gp.shape[3]), dtype=gp.dtype, device=gp.device)
             for aux in (mask, res):
-                if aux is not None:
-                    _dev_ok(aux)
-                    assert aux.shape == gx.shape and aux.dtype == gp.dtype and aux.is_contiguous()
+                assert aux is None or (aux.shape == gx.shape and aux.dtype == gp.dtype and aux.is_contiguous())
             gxs.append(gx)
-            masks.append(mask.data_ptr() if mask is not None else None)
-            ress.append(res.data_ptr() if res is not None else None)
-        vp, ip = ctypes.c_void_p * n, ctypes.c_int * n
+        ip = ctypes.c_int * n
         lib.call('msmc_reflect_fold_multi_tap' if tap_first else 'msmc_reflect_fold_multi_res',
-                 vp(*[t[0].data_ptr() for t in part]), vp(*masks), vp(*ress), vp(*[t.data_ptr() for t in gxs]),
+                 _pointers([t[0] for t in part]), _pointers([t[3] for t in part]), _pointers([t[4] for t in part]), _pointers(gxs),
                  ip(*[t[0].shape[0] for t in part]), ip(*[t[1] for t in part]), ip(*[t[2] for t in part]),
-                 ip(*[t[0].shape[3] for t in part]), n, p, float(slope), _DT[part[0][0].dtype], lib.stream(part[0][0]))
+                 ip(*[t[0].shape[3] for t in part]), n, p, float(slope), _DT[lead.dtype], lib.stream(lead))
         outs.extend(gxs)
     return outs
-
