@@ -1020,6 +1020,29 @@ int msmc_opt_clip_adamw(const msmc_opt_tensor* table, int ntensors, int nblocks,
                         float* norm_coef, const float* lr, float* step, float beta1, float beta2, float eps,
                         float weight_decay, int write_grads, msmc_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A1  acoustic features from waveforms in one launch (csrc/features.hip): normalised log-mel spectrogram and frame energy.
+ * Replaces melspectrogram / energy of reference examples/csmsc/scripts/audio/audio.py:23-24, 59-73, 81-85, 95-99, 114-115,
+ * 122-129 (pre-emphasis, librosa.stft with center=True, magnitude, Slaney mel, dB, normalise and clip; the l2 norm of the
+ * magnitudes per frame).
+ *   wav [B][Lmax] fp32, length [B] int32 on the device -> mel [B][Tmax][M] fp32, energy [B][Tmax] fp32 (NULL: not computed).
+ *   T_b = 1 + length[b] / hop frames per utterance; rows T_b <= t < Tmax are +0.  Every utterance is reflect-padded by
+ *   n_fft / 2 at its OWN length, and its rows do not depend on the rest of the batch or on Lmax.  An utterance whose length
+ *   is <= n_fft / 2 (after clamping to [0, Lmax]) is all zeros: the host refuses it before the launch.
+ *   basis [ceil(F / FQ)][WP][2 FQ] fp32, F = n_fft / 2 + 1, WP = win rounded up to whole KS: for frequency tile j and tap n the
+ *     FQ values w[n] cos(2 pi (n + off) f / n_fft), then the FQ values -w[n] sin(...), f = j FQ .. j FQ + FQ - 1,
+ *     off = (n_fft - win) / 2, w the periodic Hann window of win samples; zero for n >= win and f >= F.
+ *   melT [ceil(F / FQ) FQ][MP] fp32, MP = M rounded up to whole 32: the mel basis transposed, zero-padded.
+ *   FT (frames per workgroup), FQ and KS are what the tile function returns for 0, 1 and 2.
+ * Accepted: n_fft even, 1 <= win <= n_fft, hop >= 1, 1 <= M <= 128, Lmax > n_fft / 2, 1 <= B < 65536, Tmax >= 1,
+ * min_level_db < 0 < max_abs_value, and a tile's sample span ((FT - 1) min(hop, win) + WP floats) within LDS beside 49.5 KB of
+ * other buffers; otherwise MSMC_E_SHAPE and no launch.  Fixed summation orders, no atomics: the same input gives the same bits.
+ * ------------------------------------------------------------------------------------------- */
+int msmc_mel_features_tile(int which);
+int msmc_mel_features(const float* wav, const int* length, const float* basis, const float* melT, float* mel, float* energy,
+                      int B, int Lmax, int Tmax, int n_fft, int win, int hop, int M, float preemphasis, float ref_level_db,
+                      float min_level_db, float max_abs_value, int symmetric, msmc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

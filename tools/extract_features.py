@@ -1,0 +1,92 @@
+#!/usr/bin/env python
+"""Turns a directory of wavs into the ``mel/<id>.npy`` (and ``energy/<id>.npy``) files ``MelDataset``, ``TTSDataset`` and
+``EmbDataset`` read, on the gfx950 kernel (``FeatureExtractor``, msmctts_amd/hip/features.py) -- the first step of every recipe of
+the reference (examples/csmsc/scripts/audio/melspectrogram.py on a CPU process pool).
+
+    python tools/extract_features.py wav_dir -o out_dir [--energy] [--jobs 16] [--config hparams.yaml]
+
+Every ``wav_dir/<id>.wav`` is read through ``datasets/readers.py`` (first channel, integer PCM scaled to [-1, 1)).  A file whose
+sample rate is not ``sample_rate`` is refused by name: resampling is not done here (the reference resamples inside
+``librosa.load``).  The files are sorted by length and ``--jobs B`` of them share a launch; an utterance's features do not depend
+on its batch.  Writes ``out_dir/mel/<id>.npy`` float32 [T, num_mels] and, with ``--energy``, ``out_dir/energy/<id>.npy`` float32
+[T], T = 1 + samples // hop.  ``--config``: a yaml file naming some of the reference's hparams (``sample_rate``, ``num_mels``,
+``num_freq``, ``frame_length_ms``, ``frame_shift_ms``, ``preemphasis``, ``min_level_db``, ``ref_level_db``, ``max_abs_value``,
+``symmetric_specs``), at the top level or under ``hparams``; the rest keep the defaults of hparams.py.  Prints the files, frames
+and seconds of audio per second of wall time, reading and writing included.
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'msmc-tts_amd')]
+import msmctts_amd  # noqa: E402,F401
+import numpy as np  # noqa: E402
+
+
+def list_wavs(wav_dir):
+    """[(id, path)] of the .wav files of a directory, sorted by name"""
+    names = sorted(n for n in os.listdir(wav_dir) if n.lower().endswith('.wav'))
+    return [(n[:-4], os.path.join(wav_dir, n)) for n in names]
+
+
+def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.stdout):
+    """-> (files, frames, samples).  Raises ``ValueError`` naming the first file at another sample rate before anything is written."""
+    from msmctts_amd.datasets import readers
+    items = []
+    for uid, path in list_wavs(wav_dir):
+        wav, rate = readers.read_wav(path)
+        if rate != extractor.sample_rate:
+            raise ValueError('%s: sample rate %d, the features are defined at %d (resample it first)'
+                             % (path, rate, extractor.sample_rate))
+        items.append((uid, wav[:, 0]))
+    if not items:
+        raise ValueError('%s holds no .wav file' % wav_dir)
+    os.makedirs(os.path.join(output_dir, 'mel'), exist_ok=True)
+    if energy:
+        os.makedirs(os.path.join(output_dir, 'energy'), exist_ok=True)
+    items.sort(key=lambda it: (len(it[1]), it[0]))
+    start = time.time()
+    frames = samples = 0
+    for first in range(0, len(items), jobs):
+        batch = items[first:first + jobs]
+        mel, en, length = extractor.extract([w for _, w in batch], energy=energy)
+        mel, length = mel.cpu().numpy(), length.cpu().tolist()
+        en = en.cpu().numpy() if energy else None
+        for b, (uid, w) in enumerate(batch):
+            T = int(length[b])
+            np.save(os.path.join(output_dir, 'mel', uid + '.npy'), np.ascontiguousarray(mel[b, :T], dtype=np.float32))
+            if energy:
+                np.save(os.path.join(output_dir, 'energy', uid + '.npy'), np.ascontiguousarray(en[b, :T], dtype=np.float32))
+            frames, samples = frames + T, samples + len(w)
+    took = max(time.time() - start, 1e-9)
+    print('%d files, %d frames, %.1f s of audio in %.3f s: %.1f files/s, %.0f frames/s, %.1f audio-seconds/s'
+          % (len(items), frames, samples / extractor.sample_rate, took, len(items) / took, frames / took,
+             samples / extractor.sample_rate / took), file=out)
+    return len(items), frames, samples
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n\n')[0])
+    ap.add_argument('wav_dir')
+    ap.add_argument('-o', '--output-dir', required=True)
+    ap.add_argument('--energy', action='store_true', help='also write energy/<id>.npy')
+    ap.add_argument('-j', '--jobs', type=int, default=16, help='utterances per launch')
+    ap.add_argument('-c', '--config', default=None, help='yaml file with hparams (default: those of the reference)')
+    ap.add_argument('--device', default='cuda', help='default: the current GPU')
+    args = ap.parse_args(argv)
+    if args.jobs < 1:
+        ap.error('--jobs must be positive')
+    from msmctts_amd.hip.features import FeatureExtractor
+    conf = {}
+    if args.config is not None:
+        import yaml
+        with open(args.config) as f:
+            conf = yaml.safe_load(f) or {}
+    extractor = FeatureExtractor.from_config(conf, device=args.device)
+    return extract_dir(extractor, args.wav_dir, args.output_dir, args.energy, args.jobs)
+
+
+if __name__ == '__main__':
+    main()
