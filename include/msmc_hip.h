@@ -1043,6 +1043,30 @@ int msmc_mel_features(const float* wav, const int* length, const float* basis, c
                       int B, int Lmax, int Tmax, int n_fft, int win, int hop, int M, float preemphasis, float ref_level_db,
                       float min_level_db, float max_abs_value, int symmetric, msmc_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A2  YIN F0 tracks from waveforms in one launch (csrc/pitch.hip), on the frame grid of A1.  No reference counterpart: the
+ * reference ships no F0 tracker and fixes only the convention of the track (utils/audio.py lf02sinexi / lf02peakexi: natural-log
+ * F0 on voiced frames, a value <= 0 on unvoiced ones).  YIN steps 1-5 (de Cheveigne & Kawahara 2002), no pre-emphasis.
+ *   wav [B][Lmax] fp32, length [B] int32 on the device -> pitch [B][Tmax] fp32; optional (NULL: not written) voiced [B][Tmax]
+ *   uint8, aperiodicity [B][Tmax] fp32, cmnd [B][Tmax][tau_max + 2] fp32.
+ *   T_b = 1 + length[b] / hop frames per utterance; rows T_b <= t < Tmax are zero in every output.  span = W + tau_max + 1.
+ *   Frame t: x[j] = y[reflect(t hop - span / 2 + j)], reflected at 0 and at the utterance's OWN length; an utterance whose
+ *   length is <= span / 2 (after clamping to [0, Lmax]) is all zeros: the host refuses it before the launch.
+ *   d(tau) = sum_{j < W} (x[j] - x[j + tau])^2 for 1 <= tau <= tau_max + 1 (direct form: exactly 0 at the period of a periodic
+ *   frame); cmnd[tau] = d'(tau) = d(tau) tau / sum_{k <= tau} d(k) (1 at tau = 0 and where the sum is 0).  The lag is the first
+ *   tau in [tau_min, tau_max] with d' < threshold, walked up while d' falls (within tau_max); none: unvoiced.  Parabolic
+ *   refinement on d'(lag - 1 .. lag + 1), clipped to one sample; pitch = ln(sample_rate / (lag + delta)), the Hz value with
+ *   log_f0 == 0, +0 on unvoiced frames.  aperiodicity = d'(lag), on unvoiced frames the minimum of d' over [tau_min, tau_max].
+ *   The tile function returns the frames per workgroup for 0 and the lags a wave holds at a time for 1.
+ * Accepted: W, hop, Tmax, sample_rate >= 1, 1 <= B < 65536, 2 <= tau_min < tau_max, threshold > 0, Lmax > span / 2, and
+ * ((FT - 1) hop + span + FT ((tau_max + 2) | 1)) floats within 160 KB of LDS; otherwise MSMC_E_SHAPE and no launch.
+ * Fixed summation orders (csrc/pitch.hip), no atomics: the same input gives the same bits, whatever the batch.
+ * ------------------------------------------------------------------------------------------- */
+int msmc_pitch_yin_tile(int which);
+int msmc_pitch_yin(const float* wav, const int* length, float* pitch, unsigned char* voiced, float* aperiodicity, float* cmnd,
+                   int B, int Lmax, int Tmax, int W, int hop, int tau_min, int tau_max, int sample_rate, float threshold,
+                   int log_f0, msmc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

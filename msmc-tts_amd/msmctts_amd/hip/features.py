@@ -48,6 +48,47 @@ def energy_track(energy):
     return energy.unsqueeze(-1)
 
 
+def batch_waveforms(wav, lengths, device=None):
+    """a [B, L] or [L] tensor / array, or a list of 1-D waveforms -> (fp32 [B, L] tensor on ``device`` -- for a list without one:
+    the first CUDA row's device, else the current GPU --, host list of lengths); integer PCM is scaled to [-1, 1) as the wav
+    readers do.  Shared by ``FeatureExtractor`` and ``PitchExtractor`` (hip/pitch.py)."""
+    def as_f32(x):
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        if x.dtype == torch.int16:
+            return x.to(torch.float32) / 32768.0
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError('waveforms are fp32, float64 or int16, got %s' % x.dtype)
+        return x.to(torch.float32)
+
+    if isinstance(wav, (list, tuple)):
+        rows = [as_f32(x).reshape(-1) for x in wav]
+        if not rows:
+            raise ValueError('no waveforms')
+        lens = [int(r.numel()) for r in rows]
+        batch = torch.zeros((len(rows), max(lens)), dtype=torch.float32)
+        for i, r in enumerate(rows):
+            batch[i, :lens[i]] = r.cpu()
+        if lengths is not None and [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()] != lens:
+            raise ValueError('lengths %s do not match the waveforms %s' % (list(lengths), lens))
+        dev = device if device is not None else next((r.device for r in rows if r.is_cuda), 'cuda')
+        return batch.to(dev), lens
+    wav = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav))
+    if wav.dim() == 1:
+        wav = wav.unsqueeze(0)
+    if wav.dim() != 2:
+        raise ValueError('wav: expected [B, L] or [L], got %s' % (tuple(wav.shape),))
+    B, L = wav.shape
+    lens = [L] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+    if len(lens) != B:
+        raise ValueError('%d lengths for %d waveforms' % (len(lens), B))
+    if any(n > L for n in lens):
+        raise ValueError('a length of %d in a batch %d samples wide' % (max(lens), L))
+    wav = as_f32(wav)
+    if device is not None:
+        wav = wav.to(device)
+    return wav.contiguous(), lens
+
+
 class FeatureExtractor(object):
     def __init__(self, sample_rate=16000, num_mels=80, num_freq=1025, frame_length_ms=50, frame_shift_ms=12.5, preemphasis=0.97,
                  min_level_db=-100, ref_level_db=20, max_abs_value=4.0, symmetric_specs=True, win_length=None, hop_length=None,
@@ -97,42 +138,7 @@ class FeatureExtractor(object):
         return self._consts[key]
 
     def _batch(self, wav, lengths):
-        """-> (fp32 [B, L] tensor, host list of lengths); integer PCM is scaled to [-1, 1) as the wav readers do"""
-        def as_f32(x):
-            x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-            if x.dtype == torch.int16:
-                return x.to(torch.float32) / 32768.0
-            if x.dtype not in (torch.float32, torch.float64):
-                raise TypeError('waveforms are fp32, float64 or int16, got %s' % x.dtype)
-            return x.to(torch.float32)
-
-        if isinstance(wav, (list, tuple)):
-            rows = [as_f32(x).reshape(-1) for x in wav]
-            if not rows:
-                raise ValueError('no waveforms')
-            lens = [int(r.numel()) for r in rows]
-            batch = torch.zeros((len(rows), max(lens)), dtype=torch.float32)
-            for i, r in enumerate(rows):
-                batch[i, :lens[i]] = r.cpu()
-            if lengths is not None and [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()] != lens:
-                raise ValueError('lengths %s do not match the waveforms %s' % (list(lengths), lens))
-            dev = self.device if self.device is not None else next((r.device for r in rows if r.is_cuda), 'cuda')
-            return batch.to(dev), lens
-        wav = wav if torch.is_tensor(wav) else torch.from_numpy(np.ascontiguousarray(wav))
-        if wav.dim() == 1:
-            wav = wav.unsqueeze(0)
-        if wav.dim() != 2:
-            raise ValueError('wav: expected [B, L] or [L], got %s' % (tuple(wav.shape),))
-        B, L = wav.shape
-        lens = [L] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
-        if len(lens) != B:
-            raise ValueError('%d lengths for %d waveforms' % (len(lens), B))
-        if any(n > L for n in lens):
-            raise ValueError('a length of %d in a batch %d samples wide' % (max(lens), L))
-        wav = as_f32(wav)
-        if self.device is not None:
-            wav = wav.to(self.device)
-        return wav.contiguous(), lens
+        return batch_waveforms(wav, lengths, self.device)
 
     def extract(self, wav, lengths=None, energy=True, energy_track=False):
         """wav: [B, L] or [L] tensor / array, or a list of 1-D arrays / tensors (padded on the host, uploaded once) ->

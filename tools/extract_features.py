@@ -1,17 +1,22 @@
 #!/usr/bin/env python
-"""Turns a directory of wavs into the ``mel/<id>.npy`` (and ``energy/<id>.npy``) files ``MelDataset``, ``TTSDataset`` and
-``EmbDataset`` read, on the gfx950 kernel (``FeatureExtractor``, msmctts_amd/hip/features.py) -- the first step of every recipe of
-the reference (examples/csmsc/scripts/audio/melspectrogram.py on a CPU process pool).
+"""Turns a directory of wavs into the ``mel/<id>.npy`` (and ``energy/<id>.npy``, ``pitch/<id>.npy``) files ``MelDataset``,
+``TTSDataset`` and ``EmbDataset`` read, on the gfx950 kernels (``FeatureExtractor``, msmctts_amd/hip/features.py;
+``PitchExtractor``, msmctts_amd/hip/pitch.py) -- the first step of every recipe of the reference
+(examples/csmsc/scripts/audio/melspectrogram.py on a CPU process pool; the reference has no F0 tracker).
 
-    python tools/extract_features.py wav_dir -o out_dir [--energy] [--jobs 16] [--config hparams.yaml]
+    python tools/extract_features.py wav_dir -o out_dir [--energy] [--pitch [--fmin 60] [--fmax 500] [--threshold 0.15]]
+                                     [--jobs 16] [--config hparams.yaml]
 
 Every ``wav_dir/<id>.wav`` is read through ``datasets/readers.py`` (first channel, integer PCM scaled to [-1, 1)).  A file whose
 sample rate is not ``sample_rate`` is refused by name: resampling is not done here (the reference resamples inside
 ``librosa.load``).  The files are sorted by length and ``--jobs B`` of them share a launch; an utterance's features do not depend
 on its batch.  Writes ``out_dir/mel/<id>.npy`` float32 [T, num_mels] and, with ``--energy``, ``out_dir/energy/<id>.npy`` float32
-[T], T = 1 + samples // hop.  ``--config``: a yaml file naming some of the reference's hparams (``sample_rate``, ``num_mels``,
+[T], T = 1 + samples // hop.  With ``--pitch`` the same batches also give ``out_dir/pitch/<id>.npy`` float32 [T]: YIN's
+natural-log F0 on the same frame grid, 0 on unvoiced frames; ``--fmin``, ``--fmax`` and ``--threshold`` override the config's
+values.  ``--config``: a yaml file naming some of the reference's hparams (``sample_rate``, ``num_mels``,
 ``num_freq``, ``frame_length_ms``, ``frame_shift_ms``, ``preemphasis``, ``min_level_db``, ``ref_level_db``, ``max_abs_value``,
-``symmetric_specs``), at the top level or under ``hparams``; the rest keep the defaults of hparams.py.  Prints the files, frames
+``symmetric_specs``; for the pitch also ``fmin``, ``fmax``, ``threshold``), at the top level or under ``hparams``; the rest keep
+the defaults of hparams.py.  Prints the files, frames
 and seconds of audio per second of wall time, reading and writing included.
 """
 import argparse
@@ -31,9 +36,13 @@ def list_wavs(wav_dir):
     return [(n[:-4], os.path.join(wav_dir, n)) for n in names]
 
 
-def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.stdout):
-    """-> (files, frames, samples).  Raises ``ValueError`` naming the first file at another sample rate before anything is written."""
+def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.stdout, pitch=None):
+    """-> (files, frames, samples).  ``pitch``: a ``PitchExtractor`` on the extractor's sample rate and hop, or None.  Raises
+    ``ValueError`` naming the first file at another sample rate before anything is written."""
     from msmctts_amd.datasets import readers
+    if pitch is not None and (pitch.sample_rate, pitch.hop) != (extractor.sample_rate, extractor.hop):
+        raise ValueError('pitch at %d Hz with a hop of %d, mel at %d Hz with a hop of %d: the tracks would not line up'
+                         % (pitch.sample_rate, pitch.hop, extractor.sample_rate, extractor.hop))
     items = []
     for uid, path in list_wavs(wav_dir):
         wav, rate = readers.read_wav(path)
@@ -46,6 +55,8 @@ def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.s
     os.makedirs(os.path.join(output_dir, 'mel'), exist_ok=True)
     if energy:
         os.makedirs(os.path.join(output_dir, 'energy'), exist_ok=True)
+    if pitch is not None:
+        os.makedirs(os.path.join(output_dir, 'pitch'), exist_ok=True)
     items.sort(key=lambda it: (len(it[1]), it[0]))
     start = time.time()
     frames = samples = 0
@@ -54,8 +65,11 @@ def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.s
         mel, en, length = extractor.extract([w for _, w in batch], energy=energy)
         mel, length = mel.cpu().numpy(), length.cpu().tolist()
         en = en.cpu().numpy() if energy else None
+        f0 = pitch.extract([w for _, w in batch])[0].cpu().numpy() if pitch is not None else None
         for b, (uid, w) in enumerate(batch):
             T = int(length[b])
+            if pitch is not None:
+                np.save(os.path.join(output_dir, 'pitch', uid + '.npy'), np.ascontiguousarray(f0[b, :T], dtype=np.float32))
             np.save(os.path.join(output_dir, 'mel', uid + '.npy'), np.ascontiguousarray(mel[b, :T], dtype=np.float32))
             if energy:
                 np.save(os.path.join(output_dir, 'energy', uid + '.npy'), np.ascontiguousarray(en[b, :T], dtype=np.float32))
@@ -72,6 +86,10 @@ def main(argv=None):
     ap.add_argument('wav_dir')
     ap.add_argument('-o', '--output-dir', required=True)
     ap.add_argument('--energy', action='store_true', help='also write energy/<id>.npy')
+    ap.add_argument('--pitch', action='store_true', help='also write pitch/<id>.npy (YIN log-F0, 0 on unvoiced frames)')
+    ap.add_argument('--fmin', type=float, default=None, help='lowest F0 in Hz (default: the config, else 60)')
+    ap.add_argument('--fmax', type=float, default=None, help='highest F0 in Hz (default: the config, else 500)')
+    ap.add_argument('--threshold', type=float, default=None, help='threshold of YIN (default: the config, else 0.15)')
     ap.add_argument('-j', '--jobs', type=int, default=16, help='utterances per launch')
     ap.add_argument('-c', '--config', default=None, help='yaml file with hparams (default: those of the reference)')
     ap.add_argument('--device', default='cuda', help='default: the current GPU')
@@ -85,7 +103,12 @@ def main(argv=None):
         with open(args.config) as f:
             conf = yaml.safe_load(f) or {}
     extractor = FeatureExtractor.from_config(conf, device=args.device)
-    return extract_dir(extractor, args.wav_dir, args.output_dir, args.energy, args.jobs)
+    pitch = None
+    if args.pitch:
+        from msmctts_amd.hip.pitch import PitchExtractor
+        given = {k: getattr(args, k) for k in ('fmin', 'fmax', 'threshold') if getattr(args, k) is not None}
+        pitch = PitchExtractor.from_config(conf, device=args.device, **given)
+    return extract_dir(extractor, args.wav_dir, args.output_dir, args.energy, args.jobs, pitch=pitch)
 
 
 if __name__ == '__main__':
