@@ -1067,6 +1067,38 @@ int msmc_pitch_yin(const float* wav, const int* length, float* pitch, unsigned c
                    int B, int Lmax, int Tmax, int W, int hop, int tau_min, int tau_max, int sample_rate, float threshold,
                    int log_f0, msmc_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A0  waveform preparation (csrc/resample.hip; host side msmctts_amd/hip/resample.py): downmix, rational resampling and peak
+ * normalisation of a padded batch, the step that stands before A1 and A2 (reference examples/csmsc/scripts/audio/
+ * audio_normalization.sh: `sox in.wav -c 1 -r $sample_rate --norm=-7 out.wav`).  sox's own filter is not reproduced: the
+ * resampler is a Kaiser-windowed-sinc polyphase filter (definition, work mapping and summation order: the source header).
+ *   x [B][Lmax_in][C] interleaved, fp32 (x_dtype 0) or int16 (x_dtype 1: scaled by 1 / 32768); length [B] int32 on the device.
+ *   The channels of a sample are averaged, (x_0 + ... + x_{C-1}) / C in channel order in fp32 (C == 1: a plain read), then
+ *     y[b][n] = sum_{j < P} bank[p][j] xbar[q down + (p down + half) / up - j],  n = q up + p, xbar = 0 outside [0, length[b])
+ *   for n < ceil(length[b] up / down); y [B][Lmax_out] fp32 is +0 behind that.  j ascending from +0, fp32, one rounding for the
+ *   product and one for the sum.  bank [up][P] fp32: row p holds h[up j + (p down + half) % up - half], h the prototype filter
+ *   of 2 half + 1 taps at the up-sampled rate, zero past its end; P == ceil((2 half + 1) / up).
+ *   partials [B][msmc_resample_parts(...)] fp32: max |y| of each workgroup's outputs (+0 where it has none), all written.
+ *   msmc_resample_tile(which, up, down, P): 0 -> PS, the output phases a workgroup holds, 1 -> QT, the values of q it covers
+ *   (so tile borders lie at the multiples of QT up output samples); 0 for a refused shape.
+ * Accepted: no NULL operand, x_dtype 0 or 1, 1 <= B < 65536, 1 <= C <= 8, 1 <= up, down <= 1024 and coprime, half >= 0,
+ * 1 <= P <= 1024 with P == ceil((2 half + 1) / up), Lmax_in >= 1, Lmax_out >= ceil(Lmax_in up / down), Lmax_out < 2^31 - 2^21;
+ * otherwise MSMC_E_SHAPE and no launch.  ONE launch.  An utterance's samples depend neither on its batch nor on Lmax_in nor on
+ * what lies behind its length; length[b] is clamped to [0, Lmax_in].
+ * ------------------------------------------------------------------------------------------- */
+int msmc_resample_tile(int which, int up, int down, int P);
+/* the partials per utterance of a call with these shapes; 0 for a refused shape */
+int msmc_resample_parts(int Lmax_out, int up, int down, int P);
+int msmc_resample(const void* x, int x_dtype, const int* length, const float* bank, float* y, float* partials, int B, int Lmax_in,
+                  int C, int Lmax_out, int up, int down, int P, int half, msmc_stream stream);
+
+/* Peak normalisation in place, the second launch: peak_b = max over partials[b][0 .. nparts) (reduced in tile order),
+ * gain_b = target / peak_b (one IEEE division), y[b][n] *= gain_b for n < out_length[b] (clamped to [0, Lmax_out]); an utterance
+ * whose peak is 0 is left as it is.  peak [B] (may be NULL) receives peak_b.  target = fp32(10^(dB / 20)).
+ * Accepted: no NULL operand but peak, 1 <= B < 65536, Lmax_out >= 1, nparts >= 1, target > 0; otherwise MSMC_E_SHAPE, no launch. */
+int msmc_peak_scale(float* y, const float* partials, const int* out_length, float* peak, int B, int Lmax_out, int nparts, float target,
+                    msmc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

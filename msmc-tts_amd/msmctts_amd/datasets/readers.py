@@ -119,6 +119,37 @@ def read_wav(src, start=0, length=-1, shape_only=False):
             fid.close()
 
 
+def read_wav_channels(src):
+    """WAV -> (int16 or float32 [frames, channels], sample rate): every channel kept, for the downmix of hip/resample.py.  16-bit
+    PCM stays int16 (the kernel scales it by 1 / 32768, as ``read_wav`` does); every other format ``read_wav`` reads comes as
+    float32 in [-1, 1) by the same scaling."""
+    fid, owned = (src, False) if hasattr(src, 'read') else open_source(src)
+    try:
+        try:
+            with wave.open(fid, 'rb') as w:
+                ch, width, rate = w.getnchannels(), w.getsampwidth(), w.getframerate()
+                raw = w.readframes(w.getnframes())
+            if width == 1:
+                x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+            elif width == 2:
+                x = np.frombuffer(raw, dtype='<i2').astype(np.int16)
+            elif width == 3:
+                b3 = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+                v = b3[:, 0] | (b3[:, 1] << 8) | (b3[:, 2] << 16)
+                x = (v - ((v & 0x800000) << 1)).astype(np.float32) / 8388608.0
+            else:
+                x = np.frombuffer(raw, dtype='<i4').astype(np.float32) / 2147483648.0
+            return np.ascontiguousarray(x.reshape(-1, ch)), rate
+        except wave.Error:                     # not integer PCM
+            from scipy.io import wavfile
+            fid.seek(0)
+            rate, x = wavfile.read(fid)
+            return np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(len(x), -1)), rate
+    finally:
+        if owned:
+            fid.close()
+
+
 def read_torch(src, dimension=None, start=0, length=-1, shape_only=False):
     import torch
     data = torch.load(src, map_location='cpu').squeeze(0).numpy()

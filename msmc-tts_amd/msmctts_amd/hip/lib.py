@@ -239,6 +239,10 @@ _SIGNATURES.update({
     'msmc_mel_features': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _i, _vp]),
     'msmc_pitch_yin_tile': (_i, [_i]),
     'msmc_pitch_yin': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    'msmc_resample_tile': (_i, [_i, _i, _i, _i]),
+    'msmc_resample_parts': (_i, [_i, _i, _i, _i]),
+    'msmc_resample': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'msmc_peak_scale': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
 })
 
 # include/msmc_hip_debug.h: process-global A/B switches, ablation masks and the experimental fused ResBlock unit -- exported by

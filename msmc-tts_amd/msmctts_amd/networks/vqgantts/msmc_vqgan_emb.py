@@ -74,6 +74,7 @@ from ...hip import window as hipwindow
 from ...hip.kmeans import fit_kmeans, kmeans_plusplus  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
 from ...hip.features import FeatureExtractor  # noqa: F401  -- waveforms -> the mel / energy files the datasets read (hip/features.py)
 from ...hip.pitch import PitchExtractor  # noqa: F401  -- waveforms -> the pitch files, on the same frame grid (hip/pitch.py)
+from ...hip.resample import Resampler, prepare_waveforms  # noqa: F401  -- downmix, resample, peak-normalise before the two (hip/resample.py)
 from ...hip import units as hipunits
 from ...hip import vq as hipvq
 from ...hip.units import assign_units, collapse_units, unit_usage, usage_summary  # noqa: F401  -- frames -> units on that file

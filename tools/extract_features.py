@@ -5,11 +5,14 @@
 (examples/csmsc/scripts/audio/melspectrogram.py on a CPU process pool; the reference has no F0 tracker).
 
     python tools/extract_features.py wav_dir -o out_dir [--energy] [--pitch [--fmin 60] [--fmax 500] [--threshold 0.15]]
-                                     [--jobs 16] [--config hparams.yaml]
+                                     [--jobs 16] [--config hparams.yaml] [--resample [--norm -7 | --norm none]]
 
 Every ``wav_dir/<id>.wav`` is read through ``datasets/readers.py`` (first channel, integer PCM scaled to [-1, 1)).  A file whose
 sample rate is not ``sample_rate`` is refused by name: resampling is not done here (the reference resamples inside
-``librosa.load``).  The files are sorted by length and ``--jobs B`` of them share a launch; an utterance's features do not depend
+``librosa.load``) -- unless ``--resample`` is given: then every file goes through the reference's step 1 first
+(``prepare_waveforms``, msmctts_amd/hip/resample.py: all channels mixed down, resampled to ``sample_rate`` where its rate differs,
+peak-normalised to ``--norm`` dBFS, -7 as the reference, ``none`` to leave the level), as tools/prepare_wavs.py would have
+written it but without the rounding to 16 bits.  The files are sorted by length and ``--jobs B`` of them share a launch; an utterance's features do not depend
 on its batch.  Writes ``out_dir/mel/<id>.npy`` float32 [T, num_mels] and, with ``--energy``, ``out_dir/energy/<id>.npy`` float32
 [T], T = 1 + samples // hop.  With ``--pitch`` the same batches also give ``out_dir/pitch/<id>.npy`` float32 [T]: YIN's
 natural-log F0 on the same frame grid, 0 on unvoiced frames; ``--fmin``, ``--fmax`` and ``--threshold`` override the config's
@@ -36,15 +39,38 @@ def list_wavs(wav_dir):
     return [(n[:-4], os.path.join(wav_dir, n)) for n in names]
 
 
-def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.stdout, pitch=None):
+def prepared_items(extractor, wav_dir, norm_db, jobs):
+    """[(id, fp32 [L_out])]: every file through ``prepare_waveforms``, batched by source rate and channel layout"""
+    from msmctts_amd.datasets import readers
+    from msmctts_amd.hip.resample import Resampler, prepare_waveforms
+    groups = {}
+    for uid, path in list_wavs(wav_dir):
+        wav, rate = readers.read_wav_channels(path)
+        groups.setdefault((rate, wav.shape[1], wav.dtype.str), []).append((uid, wav))
+    items, resamplers = [], {}
+    for (rate, _, _), group in sorted(groups.items()):
+        if rate not in resamplers:
+            resamplers[rate] = Resampler(rate, extractor.sample_rate, device=extractor.device)
+        group.sort(key=lambda it: (len(it[1]), it[0]))
+        for first in range(0, len(group), jobs):
+            batch = group[first:first + jobs]
+            y, length = prepare_waveforms([w for _, w in batch], None, rate, extractor.sample_rate, norm_db=norm_db,
+                                          resampler=resamplers[rate])
+            y, length = y.cpu().numpy(), length.cpu().tolist()
+            items += [(uid, np.ascontiguousarray(y[b, :int(length[b])])) for b, (uid, _) in enumerate(batch)]
+    return items
+
+
+def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.stdout, pitch=None, resample=False, norm_db=-7.0):
     """-> (files, frames, samples).  ``pitch``: a ``PitchExtractor`` on the extractor's sample rate and hop, or None.  Raises
-    ``ValueError`` naming the first file at another sample rate before anything is written."""
+    ``ValueError`` naming the first file at another sample rate before anything is written, unless ``resample``: then every file
+    is mixed down, resampled where needed and peak-normalised to ``norm_db`` (None: not normalised) first."""
     from msmctts_amd.datasets import readers
     if pitch is not None and (pitch.sample_rate, pitch.hop) != (extractor.sample_rate, extractor.hop):
         raise ValueError('pitch at %d Hz with a hop of %d, mel at %d Hz with a hop of %d: the tracks would not line up'
                          % (pitch.sample_rate, pitch.hop, extractor.sample_rate, extractor.hop))
-    items = []
-    for uid, path in list_wavs(wav_dir):
+    items = prepared_items(extractor, wav_dir, norm_db, jobs) if resample else []
+    for uid, path in ([] if resample else list_wavs(wav_dir)):
         wav, rate = readers.read_wav(path)
         if rate != extractor.sample_rate:
             raise ValueError('%s: sample rate %d, the features are defined at %d (resample it first)'
@@ -90,6 +116,10 @@ def main(argv=None):
     ap.add_argument('--fmin', type=float, default=None, help='lowest F0 in Hz (default: the config, else 60)')
     ap.add_argument('--fmax', type=float, default=None, help='highest F0 in Hz (default: the config, else 500)')
     ap.add_argument('--threshold', type=float, default=None, help='threshold of YIN (default: the config, else 0.15)')
+    ap.add_argument('--resample', action='store_true',
+                    help='downmix, resample to sample_rate and peak-normalise every file first, in place of refusing other rates')
+    ap.add_argument('--norm', default=-7.0, type=lambda v: None if v.lower() == 'none' else float(v),
+                    help='with --resample: peak level in dBFS (default -7), or none')
     ap.add_argument('-j', '--jobs', type=int, default=16, help='utterances per launch')
     ap.add_argument('-c', '--config', default=None, help='yaml file with hparams (default: those of the reference)')
     ap.add_argument('--device', default='cuda', help='default: the current GPU')
@@ -108,7 +138,8 @@ def main(argv=None):
         from msmctts_amd.hip.pitch import PitchExtractor
         given = {k: getattr(args, k) for k in ('fmin', 'fmax', 'threshold') if getattr(args, k) is not None}
         pitch = PitchExtractor.from_config(conf, device=args.device, **given)
-    return extract_dir(extractor, args.wav_dir, args.output_dir, args.energy, args.jobs, pitch=pitch)
+    return extract_dir(extractor, args.wav_dir, args.output_dir, args.energy, args.jobs, pitch=pitch, resample=args.resample,
+                       norm_db=args.norm)
 
 
 if __name__ == '__main__':
