@@ -161,7 +161,8 @@ __global__ __launch_bounds__(256) void masked_mean_final_kernel(const float* __r
         out[1] = 1.f / tot / (float)C;
     }
 }
-// ga = gout * out[1] * (MODE 0: 1, MODE 1: 2 (a - b)) on valid rows, 0 on padding; gb = -ga (when asked for)
+// ga = gout * out[1] * (MODE 0: 1, MODE 1: 2 (a - b)) on valid rows, +0 on padding; gb = -ga on valid rows, +0 on padding (when
+// asked for)
 template <typename TA, typename TB, int MODE>
 __global__ __launch_bounds__(256) void masked_mean_bwd_kernel(const TA* __restrict__ a, const TB* __restrict__ b,
                                                               const void* __restrict__ len, int is64, int T, int C,
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(256) void masked_mean_bwd_kernel(const TA* __restri
         float g = 0.f;
         if (e < nv) g = MODE == 0 ? k : 2.f * (el_ld(a + base + e) - el_ld(b + base + e)) * k;
         if (ga) el_st(ga + base + e, g);
-        if (gb) el_st(gb + base + e, -g);
+        if (gb) el_st(gb + base + e, e < nv ? -g : 0.f);
     }
 }
 

@@ -582,9 +582,15 @@ def check_hip_adamw(dev):
     a = HipAdamW(mine, lr=2e-3, betas=(0.8, 0.99), eps=1e-8, weight_decay=0.01)
     b = torch.optim.AdamW(ref, lr=2e-3, betas=(0.8, 0.99), eps=1e-8, weight_decay=0.01)
     for step in range(4):
+        off = 1
         for p, q in zip(mine, ref):
             g = torch.randn_like(p) * (3.0 if step % 2 == 0 else 0.01)
-            p.grad = g.clone() if step != 2 else base[1:1 + g.numel()].view_as(g).clone()
+            if step != 2:
+                p.grad = g.clone()
+            else:                  # a view that starts one element behind a 16-byte boundary (no clone: a clone is aligned again)
+                p.grad = base[off:off + g.numel()].view_as(g)
+                assert p.grad.data_ptr() % 16 != 0
+                off += (g.numel() + 3) // 4 * 4
             q.grad = p.grad.clone()
         norm = torch.nn.utils.clip_grad_norm_(ref, 1.0)
         b.step()
