@@ -1099,6 +1099,53 @@ int msmc_resample(const void* x, int x_dtype, const int* length, const float* ba
 int msmc_peak_scale(float* y, const float* partials, const int* out_length, float* peak, int B, int Lmax_out, int nparts, float target,
                     msmc_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A4  spectrogram and Griffin-Lim (csrc/griffin_lim.hip; host side msmctts_amd/hip/griffin_lim.py), on the frame grid of A1.
+ * Replaces spectrogram, inv_preemphasis, _stft / _istft and the loops of _griffin_lim / _fast_griffin_lim of reference
+ * examples/csmsc/scripts/audio/audio.py:27-56, 71-78, 176-204 (librosa.stft + librosa.istft per iteration on the CPU).
+ *
+ * msmc_stft: wav [B][Lmax] fp32, length [B] int32 on the device; T_b = 1 + length[b] / hop frames, reflect-padded by n_fft / 2
+ * at the utterance's OWN length, pre-emphasis as in A1 (0: none), basis as in A1; z = re + i im with A1's tap order.
+ *   mode 0 (complex): out [B][Tmax][2][F] fp32 -- per frame its F real parts, then its F imaginary parts.  mag, prev NULL.
+ *   mode 1 (project): mag [B][Tmax][F] fp32; out (layout of mode 0) = t1 = mag z / |z|, (mag, 0) where z == 0 exactly; within
+ *     4 x 2^-24 mag per component of the exact quotient of the fp32 z.  With prev (layout of mode 0, holding t0; NULL: none):
+ *     out = t1 + alpha (t1 - t0), prev = t1, each element read and written by one work-item.
+ *   mode 2 (db): out [B][Tmax][F] = clip(normalise(20 log10(max(1e-5, |z|)) - ref_level_db)), A1's epilogue per frequency.
+ *   Rows T_b <= t < Tmax of out are +0; an utterance with length <= n_fft / 2 is all zero rows.  The tile function returns the
+ *   frames per workgroup, the frequencies per tile and the taps per slice for 0, 1, 2 (those of A1), and the samples per carry
+ *   step of msmc_deemphasis for 3.
+ * Accepted: mode 0..2 with mag exactly in mode 1 and prev only there, n_fft even, 1 <= win <= n_fft, hop >= 1, Lmax > n_fft / 2,
+ * 1 <= B < 65536, Tmax >= 1, in mode 2 min_level_db < 0 < max_abs_value, and a tile's sample span within LDS beside 32 KB.
+ *
+ * msmc_istft: spec [B][Tmax][2][F] fp32 (layout of mode 0), frames [B] int32 on the device (clamped to [0, Tmax]) ->
+ * y [B][hop (Tmax - 1)] fp32 = librosa.istft(hop_length, win_length) with its defaults: irfft, periodic Hann window centred in
+ * n_fft, overlap-add, division by the summed squared windows where they exceed FLT_MIN, n_fft / 2 trimmed at both ends;
+ * samples hop (frames[b] - 1) <= j are +0.
+ *   ibasis [ceil(win / 128)][KP][128] fp32, KP = 2 F rounded up to whole 16: for tap tile j and row k the 128 taps n = 128 j ..:
+ *     k < F: c_f w[n] cos(2 pi f (n + off) / n_fft) / n_fft, f = k; F <= k < 2 F: -c_f w[n] sin(...) / n_fft, f = k - F, zero for
+ *     f = 0 and f = n_fft / 2; c_f = 1 there, 2 otherwise; zero for n >= win and k >= 2 F.  wsq [win] fp32: w[n]^2.
+ *   Every sample sums the frames that cover it in ascending t, and the squared windows in the same order; a frame's taps sum
+ *   k ascending (real parts, then imaginary parts).  msmc_istft_tile: the frame positions a workgroup owns, 32 - (ceil(win / hop)
+ *   - 1); 0 for a refused geometry.
+ * Accepted: n_fft even, 1 <= win <= n_fft, hop >= 1, ceil(win / hop) <= 32, (32 win + 5184) floats within 160 KB of LDS
+ * (win <= 1118), 1 <= B < 65536, Tmax >= 2, hop (Tmax - 1) + n_fft < 2^31.
+ *
+ * msmc_deemphasis: y[b][n] = x[b][n] + coef y[b][n - 1] for n < length[b] (clamped to [0, Lmax]), x, y [B][Lmax] fp32, x == y
+ * allowed; samples at or behind the length are neither read nor written.  Order: the source header.
+ * Accepted: no NULL operand, 1 <= B < 65536, Lmax >= 1.
+ *
+ * All three: otherwise MSMC_E_SHAPE and no launch; ONE launch each; fixed summation orders, no atomics; an utterance's values
+ * depend on its own samples / frames and length only, not on the batch or the padding.
+ * ------------------------------------------------------------------------------------------- */
+int msmc_stft_tile(int which);
+int msmc_stft(const float* wav, const int* length, const float* basis, int mode, float* out, const float* mag, float* prev,
+              float alpha, int B, int Lmax, int Tmax, int n_fft, int win, int hop, float preemphasis, float ref_level_db,
+              float min_level_db, float max_abs_value, int symmetric, msmc_stream stream);
+int msmc_istft_tile(int n_fft, int win, int hop);
+int msmc_istft(const float* spec, const int* frames, const float* ibasis, const float* wsq, float* y, int B, int Tmax, int n_fft,
+               int win, int hop, msmc_stream stream);
+int msmc_deemphasis(const float* x, float* y, const int* length, int B, int Lmax, float coef, msmc_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

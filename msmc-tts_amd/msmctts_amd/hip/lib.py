@@ -243,6 +243,11 @@ _SIGNATURES.update({
     'msmc_resample_parts': (_i, [_i, _i, _i, _i]),
     'msmc_resample': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'msmc_peak_scale': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    'msmc_stft_tile': (_i, [_i]),
+    'msmc_stft': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _i, _vp]),
+    'msmc_istft_tile': (_i, [_i, _i, _i]),
+    'msmc_istft': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'msmc_deemphasis': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp]),
 })
 
 # include/msmc_hip_debug.h: process-global A/B switches, ablation masks and the experimental fused ResBlock unit -- exported by

@@ -73,6 +73,7 @@ from ...hip import unit_ce as hipunitce
 from ...hip import window as hipwindow
 from ...hip.kmeans import fit_kmeans, kmeans_plusplus  # noqa: F401  -- fits the file ``KMeansQuantizer`` loads (``fit_kmeans(...).save(path)``)
 from ...hip.features import FeatureExtractor  # noqa: F401  -- waveforms -> the mel / energy files the datasets read (hip/features.py)
+from ...hip.griffin_lim import GriffinLim  # noqa: F401  -- and back: spectrogram / mel -> waveform by Griffin-Lim (hip/griffin_lim.py)
 from ...hip.pitch import PitchExtractor  # noqa: F401  -- waveforms -> the pitch files, on the same frame grid (hip/pitch.py)
 from ...hip.resample import Resampler, prepare_waveforms  # noqa: F401  -- downmix, resample, peak-normalise before the two (hip/resample.py)
 from ...hip import units as hipunits

@@ -5,7 +5,7 @@
 (examples/csmsc/scripts/audio/melspectrogram.py on a CPU process pool; the reference has no F0 tracker).
 
     python tools/extract_features.py wav_dir -o out_dir [--energy] [--pitch [--fmin 60] [--fmax 500] [--threshold 0.15]]
-                                     [--jobs 16] [--config hparams.yaml] [--resample [--norm -7 | --norm none]]
+                                     [--spectrogram] [--jobs 16] [--config hparams.yaml] [--resample [--norm -7 | --norm none]]
 
 Every ``wav_dir/<id>.wav`` is read through ``datasets/readers.py`` (first channel, integer PCM scaled to [-1, 1)).  A file whose
 sample rate is not ``sample_rate`` is refused by name: resampling is not done here (the reference resamples inside
@@ -16,7 +16,9 @@ written it but without the rounding to 16 bits.  The files are sorted by length 
 on its batch.  Writes ``out_dir/mel/<id>.npy`` float32 [T, num_mels] and, with ``--energy``, ``out_dir/energy/<id>.npy`` float32
 [T], T = 1 + samples // hop.  With ``--pitch`` the same batches also give ``out_dir/pitch/<id>.npy`` float32 [T]: YIN's
 natural-log F0 on the same frame grid, 0 on unvoiced frames; ``--fmin``, ``--fmax`` and ``--threshold`` override the config's
-values.  ``--config``: a yaml file naming some of the reference's hparams (``sample_rate``, ``num_mels``,
+values.  With ``--spectrogram`` the same batches also give ``out_dir/spec/<id>.npy`` float32 [T, num_freq]: the reference's
+``audio.spectrogram`` (``GriffinLim.spectrogram``, msmctts_amd/hip/griffin_lim.py), what tools/invert_features.py --linear
+reads.  ``--config``: a yaml file naming some of the reference's hparams (``sample_rate``, ``num_mels``,
 ``num_freq``, ``frame_length_ms``, ``frame_shift_ms``, ``preemphasis``, ``min_level_db``, ``ref_level_db``, ``max_abs_value``,
 ``symmetric_specs``; for the pitch also ``fmin``, ``fmax``, ``threshold``), at the top level or under ``hparams``; the rest keep
 the defaults of hparams.py.  Prints the files, frames
@@ -61,8 +63,10 @@ def prepared_items(extractor, wav_dir, norm_db, jobs):
     return items
 
 
-def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.stdout, pitch=None, resample=False, norm_db=-7.0):
-    """-> (files, frames, samples).  ``pitch``: a ``PitchExtractor`` on the extractor's sample rate and hop, or None.  Raises
+def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.stdout, pitch=None, resample=False, norm_db=-7.0,
+                spectrogram=None):
+    """-> (files, frames, samples).  ``pitch``: a ``PitchExtractor`` on the extractor's sample rate and hop, or None;
+    ``spectrogram``: a ``GriffinLim`` of the extractor's hparams, or None.  Raises
     ``ValueError`` naming the first file at another sample rate before anything is written, unless ``resample``: then every file
     is mixed down, resampled where needed and peak-normalised to ``norm_db`` (None: not normalised) first."""
     from msmctts_amd.datasets import readers
@@ -83,6 +87,8 @@ def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.s
         os.makedirs(os.path.join(output_dir, 'energy'), exist_ok=True)
     if pitch is not None:
         os.makedirs(os.path.join(output_dir, 'pitch'), exist_ok=True)
+    if spectrogram is not None:
+        os.makedirs(os.path.join(output_dir, 'spec'), exist_ok=True)
     items.sort(key=lambda it: (len(it[1]), it[0]))
     start = time.time()
     frames = samples = 0
@@ -92,8 +98,11 @@ def extract_dir(extractor, wav_dir, output_dir, energy=False, jobs=16, out=sys.s
         mel, length = mel.cpu().numpy(), length.cpu().tolist()
         en = en.cpu().numpy() if energy else None
         f0 = pitch.extract([w for _, w in batch])[0].cpu().numpy() if pitch is not None else None
+        sp = spectrogram.spectrogram([w for _, w in batch])[0].cpu().numpy() if spectrogram is not None else None
         for b, (uid, w) in enumerate(batch):
             T = int(length[b])
+            if spectrogram is not None:
+                np.save(os.path.join(output_dir, 'spec', uid + '.npy'), np.ascontiguousarray(sp[b, :T], dtype=np.float32))
             if pitch is not None:
                 np.save(os.path.join(output_dir, 'pitch', uid + '.npy'), np.ascontiguousarray(f0[b, :T], dtype=np.float32))
             np.save(os.path.join(output_dir, 'mel', uid + '.npy'), np.ascontiguousarray(mel[b, :T], dtype=np.float32))
@@ -116,6 +125,7 @@ def main(argv=None):
     ap.add_argument('--fmin', type=float, default=None, help='lowest F0 in Hz (default: the config, else 60)')
     ap.add_argument('--fmax', type=float, default=None, help='highest F0 in Hz (default: the config, else 500)')
     ap.add_argument('--threshold', type=float, default=None, help='threshold of YIN (default: the config, else 0.15)')
+    ap.add_argument('--spectrogram', action='store_true', help='also write spec/<id>.npy (the normalised linear spectrogram)')
     ap.add_argument('--resample', action='store_true',
                     help='downmix, resample to sample_rate and peak-normalise every file first, in place of refusing other rates')
     ap.add_argument('--norm', default=-7.0, type=lambda v: None if v.lower() == 'none' else float(v),
@@ -138,8 +148,12 @@ def main(argv=None):
         from msmctts_amd.hip.pitch import PitchExtractor
         given = {k: getattr(args, k) for k in ('fmin', 'fmax', 'threshold') if getattr(args, k) is not None}
         pitch = PitchExtractor.from_config(conf, device=args.device, **given)
+    spectrogram = None
+    if args.spectrogram:
+        from msmctts_amd.hip.griffin_lim import GriffinLim
+        spectrogram = GriffinLim.from_config(conf, device=args.device)
     return extract_dir(extractor, args.wav_dir, args.output_dir, args.energy, args.jobs, pitch=pitch, resample=args.resample,
-                       norm_db=args.norm)
+                       norm_db=args.norm, spectrogram=spectrogram)
 
 
 if __name__ == '__main__':
